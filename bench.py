@@ -3,8 +3,13 @@ fwd/bwd + SGD + ProposalLayer with 3-D NMS) on synthetic 128^3 volumes
 (BASELINE.json configs[1]), one process per GPU (weak scaling, data parallel
 over RCCL), plus the 3-D PyramidROIAlign HBM roofline (configs[2] shapes).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 128]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size 128] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline
+result; --dump-outputs DIR also writes what the last timed step returned.
+Every other leg (eager comparison, rooflines, depth slab, configs[0],
+inference, ROIAlign, NMS, CPU baselines) runs only with --full.
 
 Rank 0 prints ONE JSON line.
 """
@@ -1134,6 +1139,31 @@ def deterministic_leg(step, steps, warmup):
     return {"ms_per_step": round(el / steps * 1e3, 2), "steps": steps, "scratch_mb": 256}
 
 
+DUMP_WEIGHT_SAMPLES = 1 << 20
+
+
+def dump_outputs(path, result, model):
+    """What the last timed step handed its caller, one float32 .npy per array:
+    the losses of the step's result dict (loss, rpn_class_loss, rpn_bbox_loss)
+    and, as the step updates the model in place, a fixed seeded sample of
+    DUMP_WEIGHT_SAMPLES entries of the updated flat weights (a few MB in all).
+    These repeat from run to run up to rounding: the weight gradients are
+    summed with fp32 atomics, whose order leaves about 1e-8 in the weights.
+    rpn_rois is left out: the ProposalLayer's top-k and NMS turn that rounding
+    noise in the scores into a different choice of boxes (two runs of one
+    build: 1 box of 6000 exchanged, every row after it shifted), so it cannot
+    be compared value for value; tests/test_gpu_roi_nms.py pins it bit for bit
+    on fixed inputs instead."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v for k, v in result.items() if v is not None and k != "rpn_rois"}
+    flat = model.store.flat.detach().reshape(-1)
+    idx = np.random.default_rng(0).choice(flat.numel(), size=min(DUMP_WEIGHT_SAMPLES, flat.numel()), replace=False)
+    arrays["weights_sample"] = flat[torch.from_numpy(np.sort(idx)).to(flat.device)]
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.atleast_1d(t.detach().float().cpu().numpy()))
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1143,7 +1173,13 @@ def main():
     ap.add_argument("--no-proposals", action="store_true")
     ap.add_argument("--slab-size", type=int, default=256,
                     help="depth-slab leg volume size (configs[4]); 0 disables the leg")
-    ap.add_argument("--no-extras", action="store_true", help="skip roofline / ROIAlign / CPU legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run, also every other leg: eager comparison, rooflines, depth slab, "
+                         "configs[0], inference, ROIAlign, NMS, CPU baselines")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the roofline / ROIAlign / CPU legs (a plain run has none)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32)")
     ap.add_argument("--roi-size", type=int, default=256, help="large-volume ROIAlign leg (0: off)")
     ap.add_argument("--infer-size", type=int, default=256, help="MaskRCNN inference leg size (0: off)")
     ap.add_argument("--cpu-slab", type=int, default=0, help="CPU-baseline depth slab (0: whole volume)")
@@ -1152,6 +1188,9 @@ def main():
     ap.add_argument("--wgrad-inline", action="store_true",
                     help="weight gradients on the compute stream (serialized kernel traces)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    extras = args.full and not args.no_extras
     if args.wgrad_inline:
         from m3d import nn as mnn
         mnn.WGRAD_STREAM = False
@@ -1215,6 +1254,7 @@ def main():
     ms = el / args.steps * 1e3
     value = world * args.steps / el
     log(f"[bench] {ms:.1f} ms/step, {value:.3f} volumes/s, loss {float(r['loss']):.4f}")
+    dumped = dump_outputs(args.dump_outputs, r, model) if args.dump_outputs and rank == 0 else None
 
     out = {"metric": METRIC, "value": round(value, 4), "unit": "volumes/s", "n_gpus": world,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 2),
@@ -1228,7 +1268,9 @@ def main():
                       "hip_graph": use_graph}}
     if graph_error is not None:
         out["config"]["hip_graph_error"] = graph_error
-    if use_graph:
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
+    if use_graph and args.full:
         # the same step launched eagerly, timed the same way (for comparison only)
         for _ in range(2):
             eager_step()
@@ -1239,7 +1281,7 @@ def main():
         torch.cuda.synchronize()
         out["eager_ms_per_step"] = round((time.perf_counter() - t0) / args.steps * 1e3, 2)
         model._graph = step = None              # release the replay's private pool before the legs
-    if world == 1 and not args.no_extras:
+    if world == 1 and extras:
         try:
             out["step_roofline"] = step_roofline(model, eager_step, ms, os.environ.get("M3D_STEP_ROOFLINE_TABLE"))
         except Exception as e:  # report, never hide
@@ -1248,7 +1290,7 @@ def main():
         v = validate_dp(model, world)
         out.setdefault("validation", {})["dp"] = v
         log(f"[bench] dp validation: {json.dumps(v)}")
-    if world > 1 and not args.no_extras:
+    if world > 1 and extras:
         try:
             ar = time_allreduce(model.store.grad_flat, world)
         except Exception as e:  # report, never hide
@@ -1256,7 +1298,7 @@ def main():
         if rank == 0:
             out["allreduce"] = ar
             out["validation"]["dp"]["allreduce_bus_GBps"] = ar.get("bus_GBps")
-    if args.slab_size and not args.no_extras:
+    if args.slab_size and extras:
         log(f"[bench] leg depth_slab {args.slab_size}^3 ({time.strftime('%H:%M:%S')})")
         del r
         torch.cuda.empty_cache()
@@ -1271,7 +1313,7 @@ def main():
                     out.setdefault("validation", {})["depth_slab"] = out["depth_slab"]["validation"]
         except Exception as e:  # report, never hide
             out["depth_slab"] = {"error": repr(e)}
-    if world == 1 and not args.no_extras:
+    if world == 1 and extras:
         try:
             log(f"[bench] leg configs0 ({time.strftime('%H:%M:%S')})")
             out["configs0"] = configs0_leg(dev, max(3, args.steps // 2), 2)
@@ -1287,7 +1329,7 @@ def main():
             out["deterministic"] = deterministic_leg(eager_step, max(3, args.steps // 2), 2)
         except Exception as e:  # report, never hide
             out["deterministic"] = {"error": repr(e)}
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and extras:
         with torch.no_grad():
             fmaps = model.features(image)
         try:
