@@ -175,6 +175,17 @@ def test_maxpool_same_and_subsample(cuda, C):
         return                                   # subsample221 is float4-only
     s = subsample221(xg)
     np.testing.assert_array_equal(s.detach().cpu().numpy(), x[:, ::2, ::2].numpy())
+    # odd H and W (the last row / column is kept: OH = (H + 1) // 2), forward and backward
+    xo = torch.tensor(rng.normal(size=(2, 9, 7, 5, C)), dtype=torch.float32)
+    xog = xo.to(cuda).requires_grad_(True)
+    so = subsample221(xog)
+    assert tuple(so.shape) == (2, 5, 4, 5, C)
+    np.testing.assert_array_equal(so.detach().cpu().numpy(), xo[:, ::2, ::2].numpy())
+    go = torch.tensor(rng.normal(size=so.shape), dtype=torch.float32)
+    so.backward(go.to(cuda))
+    want = torch.zeros_like(xo)
+    want[:, ::2, ::2] = go
+    np.testing.assert_array_equal(xog.grad.cpu().numpy(), want.numpy())
 
 
 @pytest.mark.parametrize("shape", [(1, 16, 16, 21, 64), (2, 9, 7, 8, 16), (1, 12, 10, 3, 32)])
