@@ -6,6 +6,9 @@ Drop-in surface:
   m3d.layers   ProposalLayer, PyramidROIAlign (core/models.py:369-503, 597-687)
   m3d.backbone ResNet3D (resnet_graph), FPN, RPNHead (build_rpn_model)
   m3d.model    RPN training model, losses, synthetic inputs
+  m3d.heads    classifier / mask heads, DetectionLayer, MaskRCNN (detect, head_losses)
+  m3d.head_losses  mrcnn_losses (+ mrcnn_class_loss / mrcnn_bbox_loss / mrcnn_mask_loss,
+               active_class_ids_from_meta): core/models.py:1676-1960, value + gradient
   m3d.config   Config / load_config (core/config.py)
   m3d.parallel depth-slab sharding + RCCL gradient all-reduce
 All compute runs in libm3d.so (hand-written HIP for gfx950); there is no CPU
@@ -13,4 +16,16 @@ fallback.
 """
 from . import config  # noqa: F401
 
-__all__ = ["config", "ops", "layers", "backbone", "model", "anchors"]
+__all__ = ["config", "ops", "layers", "backbone", "model", "anchors", "heads", "head_losses", "mrcnn_losses",
+           "mrcnn_class_loss", "mrcnn_bbox_loss", "mrcnn_mask_loss", "active_class_ids_from_meta"]
+
+_HEAD_LOSS_NAMES = ("mrcnn_losses", "mrcnn_class_loss", "mrcnn_bbox_loss", "mrcnn_mask_loss",
+                    "active_class_ids_from_meta")
+
+
+def __getattr__(name):
+    """The head-loss names resolve on first use (importing m3d itself stays free of torch)."""
+    if name in _HEAD_LOSS_NAMES:
+        from . import head_losses
+        return getattr(head_losses, name)
+    raise AttributeError(f"module 'm3d' has no attribute {name!r}")

@@ -20,7 +20,9 @@ libm3d kernel:
     its post-activation residual Add fused in the epilogue, the 2x2x2 stride-2
     transposed conv as one GEMM with a scattering epilogue, the sigmoid 1^3 conv;
   * DetectionLayer: m3d_refine_detections + 2-D m3d_nms3d + m3d_detections_gather.
-Inference only (TRAIN_BN=False: BN uses moving statistics).
+Inference only (TRAIN_BN=False: BN uses moving statistics).  MaskRCNN.head_losses
+scores a checkpoint with the three head losses of the training graph
+(m3d.head_losses); the backward through the heads is out of scope.
 """
 from __future__ import annotations
 
@@ -259,6 +261,67 @@ class MaskRCNN:
         self.detection = DetectionLayer(c.BBOX_STD_DEV, float(c.DETECTION_MIN_CONFIDENCE),
                                         int(c.DETECTION_MAX_INSTANCES), float(c.DETECTION_NMS_THRESHOLD),
                                         int(c.IMAGES_PER_GPU), name="mrcnn_detection")
+        self.proposal_layer_training = self.detection_targets = None    # built by head_losses()
+
+    @torch.no_grad()
+    def head_losses(self, image, image_meta, gt_class_ids, gt_boxes, gt_masks, seed=None):
+        """The three head losses of the reference's head-training graph
+        (MaskRCNN.build, MODE "training", core/models.py:5586-5660) for one batch:
+
+          backbone + FPN + RPN -> ProposalLayer(POST_NMS_ROIS_TRAINING)
+          -> DetectionTargetLayer(config) on the pixel gt_boxes normalised by
+             (H,W,D,H,W,D) (norm_boxes_graph), gt_class_ids [B,G], gt_masks [B,H,W,D,G]
+          -> PyramidROIAlign(POOL_SIZE) / (MASK_POOL_SIZE) on the sampled ROIs
+          -> classifier head / mask head -> m3d.head_losses.mrcnn_losses
+             with active_class_ids = image_meta[:, 16:] and the config's LOSS_WEIGHTS.
+
+        Returns a dict: "loss" (weighted total), "mrcnn_class_loss",
+        "mrcnn_bbox_loss", "mrcnn_mask_loss" (device scalars) and the
+        intermediates (rpn_rois, rois, target_gt_boxes, target_class_ids,
+        target_bbox, target_mask, mrcnn_class_logits, mrcnn_class, mrcnn_bbox,
+        mrcnn_mask, active_class_ids).  ``seed`` fixes DetectionTargetLayer's
+        sampling order.
+
+        The heads run with moving-statistics BN, as everywhere in this tree.  The
+        reference's training graph runs the head BNs on batch statistics
+        (train_bn=True, core/models.py:5624,5636), so this is the validation
+        score of a checkpoint, not that graph's training-mode value."""
+        from .head_losses import LOSS_NAMES, active_class_ids_from_meta, mrcnn_losses
+        from .targets import DetectionTargetLayer
+        c = self.config
+        ops._dev(image, image_meta, gt_class_ids, gt_boxes, gt_masks)
+        _, C2, C3, C4, C5 = self.backbone(image)
+        fmaps = self.fpn(C2, C3, C4, C5)
+        _, rpn_probs, rpn_bbox = self.rpn(fmaps)
+        if self.proposal_layer_training is None:
+            self.proposal_layer_training = ProposalLayer(
+                proposal_count=c.POST_NMS_ROIS_TRAINING, nms_threshold=c.RPN_NMS_THRESHOLD,
+                pre_nms_limit=c.PRE_NMS_LIMIT, images_per_gpu=c.IMAGES_PER_GPU,
+                rpn_bbox_std_dev=c.RPN_BBOX_STD_DEV, image_depth=c.IMAGE_DEPTH, name="ROI")
+            self.detection_targets = DetectionTargetLayer(
+                c, c.TRAIN_ROIS_PER_IMAGE, c.ROI_POSITIVE_RATIO, c.BBOX_STD_DEV, c.USE_MINI_MASK, c.MASK_SHAPE,
+                c.IMAGES_PER_GPU, positive_iou_threshold=c.RPN_POSITIVE_IOU,
+                negative_iou_threshold=c.RPN_NEGATIVE_IOU, name="proposal_targets")
+        rpn_rois = self.proposal_layer_training([rpn_probs, rpn_bbox, self.anchors])
+        h, w, d = (float(v) for v in image.shape[1:4])
+        scale = torch.tensor([h, w, d, h, w, d], device=image.device, dtype=torch.float32)
+        gt_norm = gt_boxes.to(torch.float32) / scale
+        rois, target_gt_boxes, target_class_ids, target_bbox, target_mask = self.detection_targets(
+            [rpn_rois, gt_class_ids, gt_norm, gt_masks], seed=seed)
+        mrcnn_maps = fmaps[:4]
+        pooled = self.roi_align_classifier([rois, image_meta] + mrcnn_maps)
+        logits, probs, bbox = self.classifier(pooled)
+        mrcnn_mask = self.mask_head(self.roi_align_mask([rois, image_meta] + mrcnn_maps))
+        active = active_class_ids_from_meta(image_meta)
+        lw = getattr(c, "LOSS_WEIGHTS", {})
+        weights = tuple(float(lw.get(n, 1.0)) for n in LOSS_NAMES)
+        total, lc, lb, lm = mrcnn_losses(target_class_ids, target_bbox, target_mask, logits, bbox, mrcnn_mask,
+                                         active, weights)
+        return {"loss": total, "mrcnn_class_loss": lc, "mrcnn_bbox_loss": lb, "mrcnn_mask_loss": lm,
+                "rpn_rois": rpn_rois, "rois": rois, "target_gt_boxes": target_gt_boxes,
+                "target_class_ids": target_class_ids, "target_bbox": target_bbox, "target_mask": target_mask,
+                "mrcnn_class_logits": logits, "mrcnn_class": probs, "mrcnn_bbox": bbox, "mrcnn_mask": mrcnn_mask,
+                "active_class_ids": active, "loss_weights": weights}
 
     def load_weights(self, filepath, by_name=True, skip_mismatch=False, exclude=()):
         """keras_model.load_weights(filepath, by_name=True, ...) on the Keras-H5 format (m3d.weights)."""

@@ -683,6 +683,43 @@ int m3d_rpn_loss_fwd(const float* logits, const float* pred, const int8_t* match
 int m3d_rpn_loss_bwd(float* g_logits, float* g_pred, int64_t A, const float* g_total, const float* scales,
                      m3d_stream_t s);
 
+/* Mask R-CNN head losses with their gradients w.r.t. the head outputs:
+ * mrcnn_class_loss_graph (core/models.py:1676-1807; focal CE on logits clipped
+ * to [-10, 10], alpha / gamma, x2 on confident false positives, active-class
+ * mask, divided by max(sum of weights, 1e-7)), mrcnn_bbox_loss_graph
+ * (core/models.py:1810-1877; 3 tanh(x / 3) soft clip + Huber over the positives)
+ * and mrcnn_mask_loss_graph (core/models.py:1881-1960; 0.3 BCE + 0.7 Dice over
+ * the positives with a non-empty target mask).  R = B * T rows, row r of image
+ * r / T.  class_logits [R,C], bbox_pred [R,C,6], mask_pred [R,V,C] (V = the
+ * mask volume mH * mW * mD, C innermost); target_class_ids [R] int32 (clamped
+ * into [0, C)), target_bbox [R,6], target_mask [R,V]; active_class_ids [B,C]
+ * floats (NULL: every class active), read at row r mod B as the reference's
+ * tf.tile does.  A branch whose prediction pointer is NULL is skipped (its loss
+ * is 0): class and bbox without mask, mask alone, ...
+ * m3d_head_loss_fwd writes the scalars total (= w_cls * class + w_box * bbox +
+ * w_mask * mask), cls_loss, box_loss, mask_loss and state [4 + 4 R] floats
+ * (16-byte aligned): the three gradient scales and the per-row mask
+ * coefficients.  m3d_head_loss_bwd takes the same inputs and that state and
+ * writes d (*g_total * total) / d prediction into every non-NULL g_logits
+ * [R,C], g_bbox [R,C,6], g_mask [R,V,C] -- each tensor whole, zeros included,
+ * so no memset is needed; *g_total is read on the device.  Fixed-order sums:
+ * run-to-run bit-identical; nothing allocates or synchronises.
+ * M3D_EINVAL before any launch: negative B / T / V, C < 2, gamma < 1, R or V
+ * beyond the grid (R * 64 and V must fit 31 bits), workspace smaller than
+ * m3d_head_loss_workspace_bytes(R, V) (which is 0 for such R / V). */
+size_t m3d_head_loss_workspace_bytes(int64_t R, int64_t V);
+int m3d_head_loss_fwd(const float* class_logits, const float* bbox_pred, const float* mask_pred,
+                      const int32_t* target_class_ids, const float* target_bbox, const float* target_mask,
+                      const float* active_class_ids, int64_t B, int64_t T, int64_t C, int64_t V,
+                      float alpha, float gamma, float w_cls, float w_box, float w_mask, float* total,
+                      float* cls_loss, float* box_loss, float* mask_loss, float* state, void* workspace,
+                      size_t ws_bytes, m3d_stream_t s);
+int m3d_head_loss_bwd(const float* class_logits, const float* bbox_pred, const float* mask_pred,
+                      const int32_t* target_class_ids, const float* target_bbox, const float* target_mask,
+                      const float* active_class_ids, int64_t B, int64_t T, int64_t C, int64_t V,
+                      float alpha, float gamma, const float* state, const float* g_total, float* g_logits,
+                      float* g_bbox, float* g_mask, m3d_stream_t s);
+
 /* ---------------------------------------------------------------------------
  * Elementwise / reduction kernels of the backbone-FPN-RPN graph.
  * ------------------------------------------------------------------------- */
