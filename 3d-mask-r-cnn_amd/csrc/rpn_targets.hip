@@ -559,6 +559,7 @@ static int rpn_targets_impl(const float* anchors, int64_t A, const float* gt_box
     if (A <= 0 || G < 0 || G > RT_MAX_G) return einval("rpn_targets: need A > 0 and 0 <= G <= 256");
     if (A > 0xFFFFFFFFll) return einval("rpn_targets: more than 2^32 anchors");
     if (total <= 0) return einval("rpn_targets: RPN_TRAIN_ANCHORS_PER_IMAGE must be positive");
+    if (atss_topk < 1) return einval("rpn_targets: ATSS_TOPK must be at least 1");   // mu = sum / k
     if (list_cap <= 0 || list_cap > 0x7FFFFFFF) return einval("rpn_targets: list_cap must be in [1, 2^31)");
     if (ws_bytes < m3d_rpn_targets_workspace_bytes(A, G, list_cap)) return einval("rpn_targets: workspace too small");
     RtWs w{};

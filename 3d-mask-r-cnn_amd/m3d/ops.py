@@ -281,7 +281,13 @@ def pyramid_roi_align(boxes, image_meta, feature_maps, pool_shape, return_levels
 def topk_keys(keys, k, positions=False):
     """tf.nn.top_k(keys, k, sorted=True) on distinct int64 keys (m3d_topk_keys,
     the hand-written radix select + rank sort; core/models.py:403-404):
-    values [k] descending, and with ``positions`` their indices in ``keys``."""
+    values [k] descending, and with ``positions`` their indices in ``keys``.
+
+    Equal keys: the values are still the k largest in descending order,
+    ``keys[positions] == values`` and the positions are pairwise distinct, and
+    every key strictly above the k-th value is selected; WHICH of the keys
+    equal to the k-th value are taken, and the order of positions among equal
+    keys, follow atomic arrival and may differ from run to run."""
     keys = _c(keys, torch.int64)
     n = keys.shape[0]
     vals = torch.empty(k, device=keys.device, dtype=torch.int64)

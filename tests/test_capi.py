@@ -170,6 +170,21 @@ def test_det_argument_is_validated():
         assert rc == -1 and b"det->scratch" in L.m3d_last_error()
 
 
+def test_rpn_targets_rejects_atss_topk_below_one():
+    """ATSS_TOPK < 1 would reach mu = sum / 0 in atss_kernel: both entry points
+    return M3D_EINVAL before anything is enqueued (no GPU touched); the same
+    call with ATSS_TOPK = 1 gets past that check, to the workspace one."""
+    import m3d._lib as lib
+    L = lib.load()
+    sd = (lib.c_f * 6)(*([0.1] * 6))
+    for fn in (L.m3d_rpn_targets, L.m3d_rpn_targets_async):
+        for topk in (0, -3):
+            rc = fn(None, 100, None, 2, 0.3, 0.1, 64, 0.5, topk, 4, sd, 0, None, None, 100, None, 0, None, None)
+            assert rc == -1 and b"ATSS_TOPK" in L.m3d_last_error()
+        rc = fn(None, 100, None, 2, 0.3, 0.1, 64, 0.5, 1, 4, sd, 0, None, None, 100, None, 0, None, None)
+        assert rc == -1 and b"workspace too small" in L.m3d_last_error()
+
+
 def test_wino_dgrad_workspace_follows_the_call_tile():
     """a data-gradient call's tile_y sets its U / M layout, so its
     workspace check must use that tile, not the library default.  The
