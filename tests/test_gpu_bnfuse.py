@@ -64,6 +64,7 @@ CASES = [
     ("direct", 1, 512, 256, 2, 4, 4, 8, 0, False, False, True),     # no ReLU, no gamma sum
     ("direct", 3, 32, 64, 1, 6, 6, 8, 0, True, True, False),        # 3^3 implicit-GEMM data gradient
     ("direct", 1, 4, 32, 1, 5, 3, 7, 0, True, True, True),          # ragged rows, 4 channels
+    ("direct", 1, 256, 32, 1, 32, 32, 32, 0, True, True, False),    # 512 blocks of 128 rows: the 128x128 tile
     ("wino", 3, 64, 64, 1, 8, 8, 16, 0, True, True, False),         # res2 2b: 4 tiles per block row
     ("wino", 3, 256, 256, 1, 6, 10, 12, 0, True, True, False),      # one tile per partial row
     ("wino", 3, 512, 512, 1, 4, 4, 8, 1, True, False, True),        # res5-like, accumulated

@@ -146,6 +146,27 @@ def test_direct_wgrad_halo_equals_extended(cuda, has_lo, has_hi):
     assert float((dw.double().cpu() - ref).abs().max()) <= 1e-5 * float(ref.abs().max())
 
 
+def test_direct_wgrad_halo_wide_equals_extended(cuda):
+    """Cout > 64: the 128x128 tile of the halo weight gradient (conv_wgrad_kernel<128, 128, vec, HALO>;
+    the test above reaches <128, 64> only), K = 27 * 36 and N = 68 ragged in both tile directions."""
+    from m3d import _lib
+    L = _lib.load()
+    g = torch.Generator(device=cuda).manual_seed(10)
+    B, H, W, D, Cin, Cout, r = 2, 5, 6, 7, 36, 68, 1
+    x = torch.randn((B, H, W, D, Cin), device=cuda, generator=g)
+    halo = torch.randn((B, H, W, 2 * r, Cin), device=cuda, generator=g)
+    dz = torch.randn((B, H, W, D, Cout), device=cuda, generator=g)
+    dw = torch.zeros((3, 3, 3, Cin, Cout), device=cuda)
+    dwe = torch.zeros_like(dw)
+    _lib.check(L.m3d_conv3d_bwd_weight_halo(x.data_ptr(), halo.data_ptr(), 1, 1, r, dz.data_ptr(), B, H, W, D, Cin,
+                                            3, 3, 3, Cout, H, W, D, 1, 1, 1, 1, 1, 1, dw.data_ptr(), _lib.stream()))
+    xe = _ext(x, halo, 1, 1, r)
+    _lib.check(L.m3d_conv3d_bwd_weight(xe.data_ptr(), dz.data_ptr(), B, H, W, xe.shape[3], Cin, 3, 3, 3, Cout, H, W,
+                                       D, 1, 1, 1, 1, 1, 0, dwe.data_ptr(), _lib.stream()))
+    torch.cuda.synchronize()
+    assert float((dw - dwe).abs().max()) <= 1e-5 * float(dwe.abs().max())
+
+
 @pytest.mark.parametrize("has_lo,has_hi,Dl", [(1, 1, 16), (0, 1, 8), (1, 0, 4), (1, 1, 12)])
 def test_wino_halo_phases_equal_one_launch(cuda, has_lo, has_hi, Dl):
     """m3d_conv3d_fwd_wino_halo_phase 1 (weights + interior z tiles, before the
