@@ -4,6 +4,10 @@
 //
 //   head_outputs_kernel   fpn_classifier_graph tail (core/models.py:1146-1186):
 //                         clip(logits, -10, 10), softmax, bbox reshape
+//   head_outputs_bwd_kernel  its backward into the Dense GEMM's output layout
+//                         (clip gradient, bbox reshape, zero padding columns)
+//   max_norm_kernel       keras.constraints.MaxNorm(axis=0) of the two Dense
+//                         kernels after an optimizer step (core/models.py:1160, 1175)
 //   refine_kernel         refine_detections_graph per-ROI part
 //                         (core/models.py:1415-1500): confidence filter, class-1
 //                         deltas, denorm, apply_box_deltas_3d_graph
@@ -33,6 +37,51 @@ __global__ void head_outputs_kernel(const float* __restrict__ raw, int64_t N, in
     for (int c = 0; c < C; ++c) sum += expf(logits[i * C + c] - mx);
     for (int c = 0; c < C; ++c) probs[i * C + c] = expf(logits[i * C + c] - mx) / sum;
     for (int q = 0; q < 6 * C; ++q) bbox[i * 6 * C + q] = r[C + q];
+}
+
+// Backward of head_outputs_kernel into the layout of raw: column c < C takes
+// g_logits through tf.clip_by_value's gradient (passes where -10 <= raw <= 10,
+// taken on the pre-clip raw), columns [C, 7C) take g_bbox, the padding columns
+// [7C, ldr) are zero.  One thread per element of g_raw, written whole.
+__global__ void head_outputs_bwd_kernel(const float* __restrict__ raw, const float* __restrict__ g_logits,
+                                        const float* __restrict__ g_bbox, int64_t N, int ldr, int C,
+                                        float* __restrict__ g_raw) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N * ldr) return;
+    const int64_t n = i / ldr;
+    const int c = (int)(i - n * ldr);
+    float g = 0.0f;
+    if (c < C) {
+        const float r = raw[i];
+        g = (r >= -10.0f && r <= 10.0f) ? g_logits[n * C + c] : 0.0f;
+    } else if (c < 7 * C) {
+        g = g_bbox[n * 6 * C + (c - C)];
+    }
+    g_raw[i] = g;
+}
+
+// keras.constraints.MaxNorm(max_value, axis=0) on w [rows][cols] in place: one
+// workgroup per column j; n_j = sqrt(sum_i w_ij^2) summed in a fixed order
+// (thread t adds rows t, t + 256, ...; LDS tree), then
+// w_ij *= clip(n_j, 0, max) / (1e-7 + n_j)   (K.epsilon() = 1e-7).
+__global__ __launch_bounds__(256) void max_norm_kernel(float* __restrict__ w, int64_t rows, int64_t cols,
+                                                       float max_value) {
+    __shared__ float red[256];
+    const int64_t j = blockIdx.x;
+    float s = 0.0f;
+    for (int64_t i = threadIdx.x; i < rows; i += 256) {
+        const float v = w[i * cols + j];
+        s += v * v;
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int step = 128; step > 0; step >>= 1) {
+        if ((int)threadIdx.x < step) red[threadIdx.x] += red[threadIdx.x + step];
+        __syncthreads();
+    }
+    const float n = sqrtf(red[0]);
+    const float scale = smin(smax(n, 0.0f), max_value) / (1e-7f + n);
+    for (int64_t i = threadIdx.x; i < rows; i += 256) w[i * cols + j] *= scale;
 }
 
 struct F6 { float v[6]; };
@@ -114,6 +163,23 @@ extern "C" int m3d_head_outputs(const float* raw, int64_t N, int64_t ldr, int32_
     hipLaunchKernelGGL(head_outputs_kernel, dim3(grid_for(N, 256)), dim3(256), 0, st(s), raw, N,
                        (int)ldr, (int)num_classes, logits, probs, bbox);
     return check_launch("head_outputs_kernel");
+}
+
+extern "C" int m3d_head_outputs_bwd(const float* raw, const float* g_logits, const float* g_bbox, int64_t N,
+                                    int64_t ldr, int32_t num_classes, float* g_raw, m3d_stream_t s) {
+    if (N < 0 || num_classes <= 0 || ldr < 7 * (int64_t)num_classes || ldr > 0x7FFFFFFF)
+        return einval("head_outputs_bwd: raw rows must hold num_classes logits + 6*num_classes deltas");
+    if (N == 0) return M3D_OK;
+    hipLaunchKernelGGL(head_outputs_bwd_kernel, dim3(grid_for(N * ldr, 256)), dim3(256), 0, st(s), raw, g_logits,
+                       g_bbox, N, (int)ldr, (int)num_classes, g_raw);
+    return check_launch("head_outputs_bwd_kernel");
+}
+
+extern "C" int m3d_max_norm(float* w, int64_t rows, int64_t cols, float max_value, m3d_stream_t s) {
+    if (rows <= 0 || cols <= 0 || cols > 0x7FFFFFFF) return einval("max_norm: rows and cols must be positive");
+    if (!(max_value >= 0.0f)) return einval("max_norm: max_value must be non-negative");
+    hipLaunchKernelGGL(max_norm_kernel, dim3((unsigned)cols), dim3(256), 0, st(s), w, rows, cols, max_value);
+    return check_launch("max_norm_kernel");
 }
 
 extern "C" int m3d_refine_detections(const float* rois, const float* probs, const float* deltas,

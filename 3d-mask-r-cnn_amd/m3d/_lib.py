@@ -151,6 +151,8 @@ _SIGS = {
                            c_i64, c_i64, c_p],
     "m3d_deconv3d_k2s2": [c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i32, c_p, c_p],
     "m3d_head_outputs": [c_p, c_i64, c_i64, c_i32, c_p, c_p, c_p, c_p],
+    "m3d_head_outputs_bwd": [c_p, c_p, c_p, c_i64, c_i64, c_i32, c_p, c_p],
+    "m3d_max_norm": [c_p, c_i64, c_i64, c_f, c_p],
     "m3d_refine_detections": [c_p, c_p, c_p, c_i64, c_i32, c_p, c_p, c_f, c_p, c_p, c_p, c_p],
     "m3d_detections_gather": [c_p, c_p, c_p, c_p, c_i32, c_p, c_p, c_p],
     "m3d_detection_targets_workspace_bytes": [c_i64],
@@ -194,6 +196,10 @@ _SIGS = {
     "m3d_bn_act_bwd_workspace_bytes": [c_i64, c_i64],
     "m3d_bn_act_bwd": [c_p, c_p, c_p, c_i64, c_i64, c_i32, c_p, c_p, c_p, c_p, c_p, c_i32, c_p,
                        c_p, c_p, c_p, c_sz, c_p],
+    "m3d_bn_train_few_rows_max": [],
+    "m3d_bn_train_workspace_bytes": [c_i64, c_i64],
+    "m3d_bn_train_fwd": [c_p, c_i64, c_i64, c_p, c_p, c_f, c_f, c_i32, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p],
+    "m3d_bn_train_bwd": [c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_sz, c_p],
     "m3d_col_sums_batched_workspace_bytes": [c_p, c_i32],
     "m3d_col_sums_batched": [c_p, c_i32, c_p, c_sz, c_p],
     "m3d_sgd_keras": [c_p, c_p, c_p, c_i64, c_p, c_p, c_i32, c_f, c_f, c_f, c_p, c_p, c_p],
@@ -212,7 +218,8 @@ _RESTYPES = {"m3d_last_error": ctypes.c_char_p, "m3d_nms3d_workspace_bytes": c_s
              "m3d_bn_act_bwd_workspace_bytes": c_sz, "m3d_bn_bwd_fused_workspace_bytes": c_sz, "m3d_conv3d_splitk_count": c_i32, "m3d_conv3d_wino_workspace_bytes": c_sz, "m3d_conv3d_wino_dgrad_workspace_bytes": c_sz, "m3d_conv3d_wino_v_bytes": c_sz,
              "m3d_conv3d_wino_u_bytes": c_sz, "m3d_conv3d_wino_tile_z": c_i32, "m3d_conv3d_wino_wgrad_tile_z": c_i32,
              "m3d_conv3d_wino_tile_y": c_i32, "m3d_conv3d_wino_dgrad_tile_y": c_i32,
-             "m3d_conv3d_wino_dgrad_tile_z": c_i32, "m3d_col_sums_batched_workspace_bytes": c_sz}
+             "m3d_conv3d_wino_dgrad_tile_z": c_i32, "m3d_col_sums_batched_workspace_bytes": c_sz,
+             "m3d_bn_train_few_rows_max": c_i64, "m3d_bn_train_workspace_bytes": c_sz}
 
 EXPORTED = tuple(_SIGS)
 

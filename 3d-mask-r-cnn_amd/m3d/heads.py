@@ -20,9 +20,16 @@ libm3d kernel:
     its post-activation residual Add fused in the epilogue, the 2x2x2 stride-2
     transposed conv as one GEMM with a scattering epilogue, the sigmoid 1^3 conv;
   * DetectionLayer: m3d_refine_detections + 2-D m3d_nms3d + m3d_detections_gather.
-Inference only (TRAIN_BN=False: BN uses moving statistics).  MaskRCNN.head_losses
-scores a checkpoint with the three head losses of the training graph
-(m3d.head_losses); the backward through the heads is out of scope.
+Inference runs every BN on moving statistics (TRAIN_BN=False).
+MaskRCNN.head_losses scores a checkpoint with the three head losses of the
+training graph (m3d.head_losses).  The classifier head also trains:
+ClassifierHead(pooled, training=True) runs its two BNs on batch statistics
+(m3d_bn_train_fwd, Keras training-mode semantics, moving statistics updated)
+and its backward (_ClassifierHeadTrain) writes the head's twelve parameter
+gradients into the ParamStore and returns the gradient of the pooled features;
+MaskRCNN.train_classifier_head is one head-only optimizer step.  The mask
+head's backward, and the join of d_pooled into PyramidROIAlign's backward and
+the trunk, are not built.
 """
 from __future__ import annotations
 
@@ -69,17 +76,43 @@ class ClassifierHead:
     def __init__(self, store, pool_size, num_classes, fc_layers_size, channels=256):
         p, fc = pool_size, fc_layers_size
         self.pool, self.C, self.fc, self.cin = p, num_classes, fc, channels
+        self.store = store
         self.conv1 = ConvLayer(store, "mrcnn_class_conv1", (p, p, p), channels, fc)
-        self.bn1 = BNLayer(store, "mrcnn_class_bn1", fc)
+        self.bn1 = BNLayer(store, "mrcnn_class_bn1", fc, momentum=0.9)      # BatchNorm(momentum=0.9)
         self.conv2 = ConvLayer(store, "mrcnn_class_conv2", (1, 1, 1), fc, fc)
-        self.bn2 = BNLayer(store, "mrcnn_class_bn2", fc)
+        self.bn2 = BNLayer(store, "mrcnn_class_bn2", fc, momentum=0.9)
         fg = 0.15
+        # the reference's prior bias is (bg, fg) for its two classes; with more classes every
+        # foreground class takes the fg value (the reference graph cannot be built there)
         self.logits = DenseLayer(store, "mrcnn_class_logits", fc, num_classes, ("normal", 0.01),
-                                 ("const", [-math.log((1 - fg) / fg), math.log(fg / (1 - fg))]))
+                                 ("const", [-math.log((1 - fg) / fg)] +
+                                  [math.log(fg / (1 - fg))] * (num_classes - 1)))
         self.bbox = DenseLayer(store, "mrcnn_bbox_fc", fc, num_classes * 6, ("normal", 0.001))
+        # kernel_constraint=MaxNorm(max_value) of the two Dense layers (core/models.py:1160, 1175)
+        self.max_norm_constraints = {"mrcnn_class_logits/kernel:0": 2.0, "mrcnn_bbox_fc/kernel:0": 1.0}
 
-    def _conv1(self, x2d):
-        """[M, K] @ [K, fc] with split-K (K = pool^3 * C is ~88k for 7^3x256)."""
+    def params(self):
+        """The head's twelve trainable tensors, in registration order."""
+        return [self.conv1.kernel, self.conv1.bias, self.bn1.gamma, self.bn1.beta,
+                self.conv2.kernel, self.conv2.bias, self.bn2.gamma, self.bn2.beta,
+                self.logits.kernel, self.logits.bias, self.bbox.kernel, self.bbox.bias]
+
+    def chunk_range(self):
+        """(first, end) chunk of the head's parameters in the finalized store:
+        they are registered consecutively, so KerasOptimizer.step(store,
+        chunks=...) on this range is a head-only step."""
+        from .params import CHUNK
+        ps = self.params()
+        i0 = self.store.params.index(ps[0])
+        if self.store.params[i0:i0 + len(ps)] != ps:
+            raise RuntimeError("classifier head parameters are not consecutive in the store")
+        last = ps[-1]
+        return ps[0].offset // CHUNK, (last.offset + -(-last.numel // CHUNK) * CHUNK) // CHUNK
+
+    def _conv1(self, x2d, bn=True):
+        """[M, K] @ [K, fc] with split-K (K = pool^3 * C is ~88k for 7^3x256).
+        bn: apply bn1's moving-statistics affine and the ReLU in the reduce
+        (inference); False: conv + bias only (the training mode's z1)."""
         L = _L()
         M, K = x2d.shape
         fc = self.fc
@@ -98,13 +131,19 @@ class ClassifierHead:
             check(L.m3d_gemm_f32_ex(x2d.data_ptr() + 4 * full * kc, K, 0, w[full * kc:].data_ptr(), 0,
                                     ws[full].data_ptr(), 0, 1, M, rem, fc, None, 0, 0, stream()),
                   "class_conv1 gemm tail")
-        scale, shift = _bn_affine(self.bn1)
+        scale, shift = _bn_affine(self.bn1) if bn else (None, None)
         h = torch.empty((M, fc), device=x2d.device, dtype=torch.float32)
         check(L.m3d_splitk_reduce(ptr(ws), splits, M, fc, ptr(self.conv1.bias.data), ptr(scale), ptr(shift),
-                                  1, ptr(h), stream()), "class_conv1 reduce")
+                                  1 if bn else 0, ptr(h), stream()), "class_conv1 reduce")
         return h
 
-    def __call__(self, pooled):
+    def __call__(self, pooled, training=False):
+        """training=False: moving-statistics BN (the inference graph).
+        training=True: batch-statistics BN over all B*N ROIs (zero-padded ones
+        included, as under TimeDistributed), the moving statistics updated once;
+        the outputs carry the head's backward (see _ClassifierHeadTrain)."""
+        if training:
+            return _ClassifierHeadTrain.apply(pooled, self.conv1.kernel.data, self)
         B, N = pooled.shape[:2]
         M = B * N
         L = _L()
@@ -133,6 +172,153 @@ class ClassifierHead:
         check(L.m3d_head_outputs(ptr(raw), M, nraw, C, ptr(logits), ptr(probs), ptr(bbox), stream()),
               "head_outputs")
         return logits, probs, bbox
+
+
+def bn_train_few_rows_max():
+    """M3D_BN_TRAIN_FEW_ROWS_MAX of the loaded library: up to this many rows
+    m3d_bn_train_fwd / _bwd run as one launch with a workgroup per 16-channel
+    strip; above it they go through per-row-block partial sums."""
+    return int(_L().m3d_bn_train_few_rows_max())
+
+
+def _bn_train_ws(M, C, dev):
+    n = int(_L().m3d_bn_train_workspace_bytes(M, C))
+    return (torch.empty(n // 4, device=dev, dtype=torch.float32) if n else None), n
+
+
+def bn_train_fwd(z, bn, relu, y=None, update_moving=True):
+    """Keras training-mode BN of z [M, C] on bn's gamma/beta (m3d_bn_train_fwd):
+    returns (y, save_mean, save_rstd); bn.moving_mean / moving_variance are
+    updated with bn.momentum unless update_moving is False.  y may be z."""
+    M, C = z.shape
+    y = torch.empty_like(z) if y is None else y
+    stats = torch.empty((2, C), device=z.device, dtype=torch.float32)
+    ws, wsb = _bn_train_ws(M, C, z.device)
+    mm, mv = (bn.moving_mean, bn.moving_variance) if update_moving else (None, None)
+    check(_L().m3d_bn_train_fwd(ptr(z), M, C, ptr(bn.gamma.data), ptr(bn.beta.data), float(bn.eps),
+                                float(bn.momentum), 1 if relu else 0, ptr(y), ptr(stats[0]), ptr(stats[1]),
+                                ptr(mm), ptr(mv), ptr(ws), wsb, stream()), "bn_train_fwd")
+    return y, stats[0], stats[1]
+
+
+def bn_train_bwd(dy, y, z, bn, mean, rstd, relu, dz=None):
+    """Backward of bn_train_fwd (m3d_bn_train_bwd): returns dz (dy itself when
+    dz is dy) and adds dgamma / dbeta into bn's ParamStore gradient views."""
+    M, C = z.shape
+    dz = torch.empty_like(dy) if dz is None else dz
+    ws, wsb = _bn_train_ws(M, C, z.device)
+    check(_L().m3d_bn_train_bwd(ptr(dy), ptr(y), ptr(z), M, C, ptr(bn.gamma.data), ptr(mean), ptr(rstd),
+                                1 if relu else 0, ptr(dz), ptr(bn.gamma.grad), ptr(bn.beta.grad), ptr(ws), wsb,
+                                stream()), "bn_train_bwd")
+    return dz
+
+
+def _dgrad1(dz, w, cin):
+    """dx [M, cin] = dz [M, cout] w^T for a Keras kernel w [cin][cout]: the 1^3
+    form of m3d_conv3d_bwd_data over M 'voxels' (cout % 32 == 0, cin % 4 == 0)."""
+    M, cout = dz.shape
+    dx = torch.empty((M, cin), device=dz.device, dtype=torch.float32)
+    check(_L().m3d_conv3d_bwd_data(ptr(dz), ptr(w), 1, 1, 1, M, cin, 1, 1, 1, cout, 1, 1, M, 1, 1, 1, 0, 0, 0,
+                                   ptr(dx), 0, stream()), "head dgrad")
+    return dx
+
+
+def _wgrad(a, b, dw):
+    """dw [K, N] += a^T b for a [M, K], b [M, N] (m3d_gemm_wgrad_f32; follows
+    the process's deterministic mode)."""
+    M, K = a.shape
+    check(_L().m3d_gemm_wgrad_f32(ptr(a), ptr(b), ptr(dw), 1, M, K, b.shape[1], stream()), "head wgrad")
+
+
+class _ClassifierHeadTrain(torch.autograd.Function):
+    """fpn_classifier_graph(train_bn=True) (core/models.py:1121-1187) with its
+    backward.  forward: conv1 (split-K GEMM + bias) -> BN1 batch statistics +
+    ReLU -> conv2 (1^3) + bias -> BN2 + ReLU -> the concatenated Dense GEMM ->
+    m3d_head_outputs.  backward (from the gradients of logits and bbox, e.g.
+    m3d.head_losses.mrcnn_losses): m3d_head_outputs_bwd (clip mask on the
+    pre-clip raw), then per layer the weight gradient (m3d_gemm_wgrad_f32), the
+    bias gradient (m3d_col_sums_batched), the data gradient (m3d_conv3d_bwd_data,
+    1^3 form) and m3d_bn_train_bwd.  The twelve parameter gradients are ADDED
+    into their ParamStore views (zero them with store.zero_grad()); the
+    returned gradient is d_pooled (only when pooled requires grad).  probs is
+    not differentiable here (the losses take the logits).  ``w`` is the conv1
+    kernel's ParamStore view: it makes the outputs part of the autograd graph."""
+
+    @staticmethod
+    def forward(ctx, pooled, w, head):
+        L = _L()
+        B, N = pooled.shape[:2]
+        M, fc, C = B * N, head.fc, head.C
+        x = pooled.detach().reshape(M, -1).contiguous()
+        dev = x.device
+        z1 = head._conv1(x, bn=False)
+        y1, mean1, rstd1 = bn_train_fwd(z1, head.bn1, True)
+        z2 = torch.empty_like(z1)
+        check(L.m3d_conv3d_fwd(ptr(y1), 1, 1, 1, M, fc, ptr(head.conv2.kernel.data), 1, 1, 1, fc,
+                               1, 1, M, 1, 1, 1, 0, 0, 0, ptr(head.conv2.bias.data), None, None, None, 0, 0,
+                               None, ptr(z2), fc, None, 0, 0, stream()), "class_conv2")
+        y2, mean2, rstd2 = bn_train_fwd(z2, head.bn2, True)
+        # raw columns padded to a multiple of 32: the data gradient g_raw Wcat^T runs
+        # on m3d_conv3d_bwd_data, whose reduction (here nraw) is a multiple of 32
+        nraw = -(-7 * C // 32) * 32
+        wcat = torch.zeros((fc, nraw), device=dev, dtype=torch.float32)
+        wcat[:, :C] = head.logits.kernel.data
+        wcat[:, C:7 * C] = head.bbox.kernel.data
+        bcat = torch.zeros((nraw,), device=dev, dtype=torch.float32)
+        bcat[:C] = head.logits.bias.data
+        bcat[C:7 * C] = head.bbox.bias.data
+        raw = torch.empty((M, nraw), device=dev, dtype=torch.float32)
+        check(L.m3d_gemm_f32_ex(ptr(y2), fc, 0, ptr(wcat), 0, ptr(raw), 0, 1, M, fc, nraw, ptr(bcat), 0, 0,
+                                stream()), "class dense")
+        logits = torch.empty((B, N, C), device=dev, dtype=torch.float32)
+        probs = torch.empty_like(logits)
+        bbox = torch.empty((B, N, C, 6), device=dev, dtype=torch.float32)
+        check(L.m3d_head_outputs(ptr(raw), M, nraw, C, ptr(logits), ptr(probs), ptr(bbox), stream()),
+              "head_outputs")
+        ctx.head, ctx.shape = head, tuple(pooled.shape)
+        ctx.save_for_backward(x, z1, y1, mean1, rstd1, z2, y2, mean2, rstd2, raw, wcat)
+        ctx.mark_non_differentiable(probs)
+        return logits, probs, bbox
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_logits, _g_probs, g_bbox):
+        from . import nn as mnn
+        L = _L()
+        head = ctx.head
+        x, z1, y1, mean1, rstd1, z2, y2, mean2, rstd2, raw, wcat = ctx.saved_tensors
+        M, nraw = raw.shape
+        fc, C, dev = head.fc, head.C, raw.device
+        g_logits = torch.zeros((M, C), device=dev) if g_logits is None else g_logits.contiguous().float()
+        g_bbox = torch.zeros((M, C, 6), device=dev) if g_bbox is None else g_bbox.contiguous().float()
+        g_raw = torch.empty_like(raw)
+        check(L.m3d_head_outputs_bwd(ptr(raw), ptr(g_logits), ptr(g_bbox), M, nraw, C, ptr(g_raw), stream()),
+              "head_outputs_bwd")
+        # the two Dense layers: kernels and biases through the concatenated layout
+        dwcat = torch.zeros_like(wcat)
+        dbcat = torch.zeros((nraw,), device=dev, dtype=torch.float32)
+        _wgrad(y2, g_raw, dwcat)
+        dy2 = _dgrad1(g_raw, wcat, fc)
+        dz2 = bn_train_bwd(dy2, y2, z2, head.bn2, mean2, rstd2, True, dz=dy2)
+        _wgrad(y1, dz2, head.conv2.kernel.grad.reshape(fc, fc))
+        dy1 = _dgrad1(dz2, head.conv2.kernel.data, fc)
+        dz1 = bn_train_bwd(dy1, y1, z1, head.bn1, mean1, rstd1, True, dz=dy1)
+        _wgrad(x, dz1, head.conv1.kernel.grad.reshape(-1, fc))
+        # the bias gradients are the column sums of dz, as TF computes them (about 0
+        # under batch statistics for the two convs)
+        sums = mnn.BiasSums()
+        sums.add(g_raw, M, nraw, dbcat)
+        sums.add(dz2, M, fc, head.conv2.bias.grad)
+        sums.add(dz1, M, fc, head.conv1.bias.grad)
+        sums.flush()
+        head.logits.kernel.grad += dwcat[:, :C]
+        head.bbox.kernel.grad += dwcat[:, C:7 * C]
+        head.logits.bias.grad += dbcat[:C]
+        head.bbox.bias.grad += dbcat[C:7 * C]
+        d_pooled = None
+        if ctx.needs_input_grad[0]:
+            d_pooled = _dgrad1(dz1, head.conv1.kernel.data, x.shape[1]).reshape(ctx.shape)
+        return d_pooled, None, None
 
 
 class MaskHead:
@@ -263,6 +449,35 @@ class MaskRCNN:
                                         int(c.IMAGES_PER_GPU), name="mrcnn_detection")
         self.proposal_layer_training = self.detection_targets = None    # built by head_losses()
 
+    def _head_targets(self, image, image_meta, gt_class_ids, gt_boxes, gt_masks, seed):
+        """The head-training graph up to the sampled ROIs and their targets
+        (core/models.py:5586-5620): trunk, ProposalLayer(POST_NMS_ROIS_TRAINING),
+        DetectionTargetLayer.  Returns (rpn_rois, rois, target_gt_boxes,
+        target_class_ids, target_bbox, target_mask, mrcnn feature maps)."""
+        from .targets import DetectionTargetLayer
+        c = self.config
+        ops._dev(image, image_meta, gt_class_ids, gt_boxes, gt_masks)
+        _, C2, C3, C4, C5 = self.backbone(image)
+        fmaps = self.fpn(C2, C3, C4, C5)
+        _, rpn_probs, rpn_bbox = self.rpn(fmaps)
+        if self.proposal_layer_training is None:
+            self.proposal_layer_training = ProposalLayer(
+                proposal_count=c.POST_NMS_ROIS_TRAINING, nms_threshold=c.RPN_NMS_THRESHOLD,
+                pre_nms_limit=c.PRE_NMS_LIMIT, images_per_gpu=c.IMAGES_PER_GPU,
+                rpn_bbox_std_dev=c.RPN_BBOX_STD_DEV, image_depth=c.IMAGE_DEPTH, name="ROI")
+            self.detection_targets = DetectionTargetLayer(
+                c, c.TRAIN_ROIS_PER_IMAGE, c.ROI_POSITIVE_RATIO, c.BBOX_STD_DEV, c.USE_MINI_MASK, c.MASK_SHAPE,
+                c.IMAGES_PER_GPU, positive_iou_threshold=c.RPN_POSITIVE_IOU,
+                negative_iou_threshold=c.RPN_NEGATIVE_IOU, name="proposal_targets")
+        rpn_rois = self.proposal_layer_training([rpn_probs, rpn_bbox, self.anchors])
+        h, w, d = (float(v) for v in image.shape[1:4])
+        scale = torch.tensor([h, w, d, h, w, d], device=image.device, dtype=torch.float32)
+        gt_norm = gt_boxes.to(torch.float32) / scale
+        rois, target_gt_boxes, target_class_ids, target_bbox, target_mask = self.detection_targets(
+            [rpn_rois, gt_class_ids, gt_norm, gt_masks], seed=seed)
+        mrcnn_maps = fmaps[:4]
+        return rpn_rois, rois, target_gt_boxes, target_class_ids, target_bbox, target_mask, mrcnn_maps
+
     @torch.no_grad()
     def head_losses(self, image, image_meta, gt_class_ids, gt_boxes, gt_masks, seed=None):
         """The three head losses of the reference's head-training graph
@@ -287,28 +502,9 @@ class MaskRCNN:
         (train_bn=True, core/models.py:5624,5636), so this is the validation
         score of a checkpoint, not that graph's training-mode value."""
         from .head_losses import LOSS_NAMES, active_class_ids_from_meta, mrcnn_losses
-        from .targets import DetectionTargetLayer
         c = self.config
-        ops._dev(image, image_meta, gt_class_ids, gt_boxes, gt_masks)
-        _, C2, C3, C4, C5 = self.backbone(image)
-        fmaps = self.fpn(C2, C3, C4, C5)
-        _, rpn_probs, rpn_bbox = self.rpn(fmaps)
-        if self.proposal_layer_training is None:
-            self.proposal_layer_training = ProposalLayer(
-                proposal_count=c.POST_NMS_ROIS_TRAINING, nms_threshold=c.RPN_NMS_THRESHOLD,
-                pre_nms_limit=c.PRE_NMS_LIMIT, images_per_gpu=c.IMAGES_PER_GPU,
-                rpn_bbox_std_dev=c.RPN_BBOX_STD_DEV, image_depth=c.IMAGE_DEPTH, name="ROI")
-            self.detection_targets = DetectionTargetLayer(
-                c, c.TRAIN_ROIS_PER_IMAGE, c.ROI_POSITIVE_RATIO, c.BBOX_STD_DEV, c.USE_MINI_MASK, c.MASK_SHAPE,
-                c.IMAGES_PER_GPU, positive_iou_threshold=c.RPN_POSITIVE_IOU,
-                negative_iou_threshold=c.RPN_NEGATIVE_IOU, name="proposal_targets")
-        rpn_rois = self.proposal_layer_training([rpn_probs, rpn_bbox, self.anchors])
-        h, w, d = (float(v) for v in image.shape[1:4])
-        scale = torch.tensor([h, w, d, h, w, d], device=image.device, dtype=torch.float32)
-        gt_norm = gt_boxes.to(torch.float32) / scale
-        rois, target_gt_boxes, target_class_ids, target_bbox, target_mask = self.detection_targets(
-            [rpn_rois, gt_class_ids, gt_norm, gt_masks], seed=seed)
-        mrcnn_maps = fmaps[:4]
+        rpn_rois, rois, target_gt_boxes, target_class_ids, target_bbox, target_mask, mrcnn_maps = \
+            self._head_targets(image, image_meta, gt_class_ids, gt_boxes, gt_masks, seed)
         pooled = self.roi_align_classifier([rois, image_meta] + mrcnn_maps)
         logits, probs, bbox = self.classifier(pooled)
         mrcnn_mask = self.mask_head(self.roi_align_mask([rois, image_meta] + mrcnn_maps))
@@ -322,6 +518,55 @@ class MaskRCNN:
                 "target_class_ids": target_class_ids, "target_bbox": target_bbox, "target_mask": target_mask,
                 "mrcnn_class_logits": logits, "mrcnn_class": probs, "mrcnn_bbox": bbox, "mrcnn_mask": mrcnn_mask,
                 "active_class_ids": active, "loss_weights": weights}
+
+    def train_classifier_head(self, image, image_meta, gt_class_ids, gt_boxes, gt_masks, optimizer, seed=None):
+        """One optimizer step on the classifier head (mrcnn_class_* and
+        mrcnn_bbox_fc) with the reference's training-mode semantics:
+
+          1. trunk, proposals, DetectionTargetLayer and PyramidROIAlign(POOL_SIZE)
+             exactly as in head_losses, under no_grad (the trunk is frozen and runs
+             on moving-statistics BN);
+          2. the classifier head in training mode (batch-statistics BN over all
+             ROIs, moving statistics updated with momentum 0.9);
+          3. mrcnn_class_loss + mrcnn_bbox_loss (LOSS_WEIGHTS; the mask branch is
+             absent);
+          4. the head's backward into the ParamStore gradients;
+          5. ``optimizer`` (a KerasOptimizer) on the head's chunk range, so the
+             store's weight-decay term applies to the head's kernels and biases;
+          6. MaxNorm on the two Dense kernels (ClassifierHead.max_norm_constraints).
+
+        Returns a dict: "loss", "mrcnn_class_loss", "mrcnn_bbox_loss" (device
+        scalars, evaluated before the update), "d_pooled" (the loss gradient with
+        respect to the pooled features [B,T,p,p,p,C]) and the sampled "rois",
+        "target_class_ids", "target_bbox".
+
+        The reference's "heads" phase (TRAIN_PHASE="heads", core/models.py:
+        5602-5668, 5764-5806) also leaves the RPN and the mask head trainable and
+        backpropagates the head losses into every trainable layer; here only the
+        classifier head moves.  d_pooled is where that backward would continue:
+        its join through PyramidROIAlign's backward into the trunk is not built."""
+        from .head_losses import LOSS_NAMES, active_class_ids_from_meta, mrcnn_losses
+        from .optim import apply_max_norm
+        c = self.config
+        ops._dev(image, image_meta, gt_class_ids, gt_boxes, gt_masks)
+        with torch.no_grad():
+            _, rois, _, target_class_ids, target_bbox, _, mrcnn_maps = \
+                self._head_targets(image, image_meta, gt_class_ids, gt_boxes, gt_masks, seed)
+            pooled = self.roi_align_classifier([rois, image_meta] + mrcnn_maps)
+        pooled = pooled.detach().requires_grad_(True)
+        lo, hi = self.classifier.chunk_range()
+        from .params import CHUNK
+        self.store.grad_flat[lo * CHUNK:hi * CHUNK].zero_()
+        logits, _, bbox = self.classifier(pooled, training=True)
+        lw = getattr(c, "LOSS_WEIGHTS", {})
+        weights = tuple(float(lw.get(n, 1.0)) for n in LOSS_NAMES)
+        total, lc, lb, _ = mrcnn_losses(target_class_ids, target_bbox, None, logits, bbox, None,
+                                        active_class_ids_from_meta(image_meta), weights)
+        total.backward()
+        optimizer.step(self.store, chunks=(lo, hi))
+        apply_max_norm(self.store, self.classifier.max_norm_constraints)
+        return {"loss": total.detach(), "mrcnn_class_loss": lc, "mrcnn_bbox_loss": lb, "d_pooled": pooled.grad,
+                "rois": rois, "target_class_ids": target_class_ids, "target_bbox": target_bbox}
 
     def load_weights(self, filepath, by_name=True, skip_mismatch=False, exclude=()):
         """keras_model.load_weights(filepath, by_name=True, ...) on the Keras-H5 format (m3d.weights)."""

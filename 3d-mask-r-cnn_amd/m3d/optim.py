@@ -94,31 +94,60 @@ class KerasOptimizer:
                 self._state = [store.moments, torch.zeros(n, dtype=torch.float32, device=dev)]
         return self._state
 
-    def step(self, store):
+    def step(self, store, chunks=None):
+        """One optimizer step.  ``chunks``: an optional contiguous range
+        (first, end) of the store's 1024-float chunks -- the kernels take base
+        pointers plus a chunk count, so a step on part of the model (e.g.
+        ClassifierHead.chunk_range(), whose parameters are registered
+        consecutively) is the same single launch on an offset view; parameters
+        and optimizer slots outside the range are not touched.  Default: the
+        whole store."""
         from . import nn as mnn
+        from .params import CHUNK
         L = _lib.load()
         s = self.state(store)
         t0 = mnn._span()
-        common = (store.n_chunks, store.seg_of_chunk.data_ptr(), store.l2_coef.data_ptr(), len(store.params))
+        c0, c1 = (0, store.n_chunks) if chunks is None else (int(chunks[0]), int(chunks[1]))
+        if not 0 <= c0 <= c1 <= store.n_chunks:
+            raise ValueError(f"chunks {chunks} outside the store's [0, {store.n_chunks}]")
+        off = 4 * CHUNK * c0
+
+        def at(t):
+            return t.data_ptr() + off
+        common = (c1 - c0, store.seg_of_chunk.data_ptr() + 4 * c0, store.l2_coef.data_ptr(), len(store.params))
         if self.kind == "SGD":
-            rc = L.m3d_sgd_keras(store.flat.data_ptr(), store.grad_flat.data_ptr(), s[0].data_ptr(), *common,
+            rc = L.m3d_sgd_keras(at(store.flat), at(store.grad_flat), at(s[0]), *common,
                                  self.current_lr(), float(self.params["momentum"]), self.clipnorm,
                                  store.norms.data_ptr(), _lib.stream())
         elif self.kind == "ADAM":
-            vhat = s[2].data_ptr() if len(s) > 2 else None
-            rc = L.m3d_adam_keras(store.flat.data_ptr(), store.grad_flat.data_ptr(), s[0].data_ptr(),
-                                  s[1].data_ptr(), vhat, *common, self.adam_lr_t(),
+            vhat = at(s[2]) if len(s) > 2 else None
+            rc = L.m3d_adam_keras(at(store.flat), at(store.grad_flat), at(s[0]),
+                                  at(s[1]), vhat, *common, self.adam_lr_t(),
                                   float(self.params["beta_1"]), float(self.params["beta_2"]),
                                   float(self.params["epsilon"]), self.clipnorm, store.norms.data_ptr(),
                                   _lib.stream())
         else:
-            rc = L.m3d_adadelta_keras(store.flat.data_ptr(), store.grad_flat.data_ptr(), s[0].data_ptr(),
-                                      s[1].data_ptr(), *common, self.current_lr(), float(self.params["rho"]),
+            rc = L.m3d_adadelta_keras(at(store.flat), at(store.grad_flat), at(s[0]),
+                                      at(s[1]), *common, self.current_lr(), float(self.params["rho"]),
                                       float(self.params["epsilon"]), self.clipnorm, store.norms.data_ptr(),
                                       _lib.stream())
         _lib.check(rc, self.kind.lower())
         # compulsory bytes: read w, g and the slots, write w and the slots (+ the clip-norm read of g)
         nslot = len(s)
-        mnn._log("optimizer", 0, 0, 4.0 * store.total * (2 + 2 * nslot + 1 + (self.clipnorm > 0)),
+        mnn._log("optimizer", 0, 0, 4.0 * CHUNK * (c1 - c0) * (2 + 2 * nslot + 1 + (self.clipnorm > 0)),
                  "optimizer", self.kind, t0)
         self.iterations += 1
+
+
+def apply_max_norm(store, constraints):
+    """keras.constraints.MaxNorm(max_value, axis=0) on the named Dense kernels
+    [in, out] of ``store``, in place (m3d_max_norm), as Keras applies a
+    kernel_constraint after every optimizer update.  ``constraints``: a dict
+    name -> max_value, e.g. ClassifierHead.max_norm_constraints."""
+    L = _lib.load()
+    for name, max_value in constraints.items():
+        p = store.by_name[name]
+        if len(p.shape) != 2:
+            raise ValueError(f"apply_max_norm: {name} is not a Dense kernel [in, out]")
+        _lib.check(L.m3d_max_norm(p.data.data_ptr(), p.shape[0], p.shape[1], float(max_value), _lib.stream()),
+                   "max_norm")

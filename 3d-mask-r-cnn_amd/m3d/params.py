@@ -41,11 +41,14 @@ class ConvLayer:
 
 
 class BNLayer:
-    """Keras BatchNormalization in inference mode (TRAIN_BN=False): frozen
-    moving statistics, trainable gamma/beta, epsilon 1e-3."""
+    """Keras BatchNormalization: trainable gamma/beta, epsilon 1e-3, moving
+    statistics.  Everywhere but the classifier head's training mode it runs in
+    inference mode (TRAIN_BN=False: frozen moving statistics); ``momentum`` is
+    the moving-average factor of a training-mode forward (Keras default 0.99;
+    BatchNorm(momentum=0.9) for mrcnn_class_bn1/2, core/models.py:1131, 1136)."""
 
-    def __init__(self, store, name, c, eps=1e-3):
-        self.name, self.c, self.eps = name, c, eps
+    def __init__(self, store, name, c, eps=1e-3, momentum=0.99):
+        self.name, self.c, self.eps, self.momentum = name, c, eps, momentum
         self.store = store
         self.aff = None            # [3, c] (rstd, scale, shift) of ParamStore.bn_affine_refresh
         self.gamma = store.add(f"{name}/gamma:0", (c,), "ones", False)

@@ -602,6 +602,20 @@ int m3d_deconv3d_k2s2(const float* x, int64_t B, int64_t H, int64_t W, int64_t D
  * ------------------------------------------------------------------------- */
 int m3d_head_outputs(const float* raw, int64_t N, int64_t ldr, int32_t num_classes, float* logits,
                      float* probs, float* bbox, m3d_stream_t s);
+/* Backward of m3d_head_outputs into the layout of raw (the gradient the
+ * concatenated Dense GEMM of fpn_classifier_graph consumes, core/models.py:
+ * 1158-1186): g_raw [N][ldr] column c < C = g_logits [N,C] where
+ * -10 <= raw <= 10 (tf.clip_by_value's gradient, taken on the pre-clip raw) and
+ * 0 outside; columns [C, 7C) = g_bbox [N,C,6]; padding columns [7C, ldr) = 0.
+ * g_raw is written whole (no memset).  ldr >= 7C. */
+int m3d_head_outputs_bwd(const float* raw, const float* g_logits, const float* g_bbox, int64_t N, int64_t ldr,
+                         int32_t num_classes, float* g_raw, m3d_stream_t s);
+/* keras.constraints.MaxNorm(max_value, axis=0) in place on a Dense kernel
+ * w [rows][cols] (kernel_constraint of mrcnn_class_logits, max 2.0, and
+ * mrcnn_bbox_fc, max 1.0: core/models.py:1160, 1175; applied after every
+ * optimizer update): n_j = sqrt(sum_i w_ij^2) in a fixed order,
+ * w_ij *= clip(n_j, 0, max_value) / (1e-7 + n_j). */
+int m3d_max_norm(float* w, int64_t rows, int64_t cols, float max_value, m3d_stream_t s);
 int m3d_refine_detections(const float* rois, const float* probs, const float* deltas, int64_t N,
                           int32_t num_classes, const float* image_meta,
                           const float bbox_std_dev[6], float min_conf, float* boxes_px,
@@ -794,6 +808,37 @@ int m3d_bn_act_bwd(const float* dy, const float* y, const float* z, int64_t M, i
                    float* dz, float* dres, int32_t accumulate_res, float* sum_dpre,
                    float* sum_dpre_xhat, float* sum_dz, void* workspace, size_t ws_bytes,
                    m3d_stream_t s);
+/* Batch-statistics BatchNorm: Keras 2.3.1 BatchNormalization.call(training=
+ * True) (TF backend, non-fused path) as the reference's head-training graph
+ * runs it under TimeDistributed (fpn_classifier_graph / build_fpn_mask_graph
+ * with train_bn=True, core/models.py:1121-1234, 5602-5668): the statistics run
+ * over all M rows of z [M, C] (M = B*N ROIs, or B*N*voxels).
+ *   forward: mean = sum z / M; var = sum (z - mean)^2 / M (biased, two passes);
+ *     rstd = 1/sqrt(var + eps); y = gamma (z - mean) rstd + beta, ReLU if relu.
+ *     save_mean / save_rstd [C] feed the backward.  moving_mean = moving_mean *
+ *     momentum + mean * (1 - momentum); moving_variance = moving_variance *
+ *     momentum + var * M / (M - (1 + eps)) * (1 - momentum), in place; both
+ *     NULL: no update.  y may alias z.
+ *   backward: dpre = dy * (y > 0) if relu (y may be NULL otherwise);
+ *     dbeta[c] += sum dpre; dgamma[c] += sum dpre * xhat (added, as the sums of
+ *     m3d_bn_act_bwd); dz = gamma rstd (dpre - sum dpre / M - xhat sum(dpre
+ *     xhat) / M).  dz may alias dy.
+ * C % 4 == 0, M >= 2 (at M = 1 Keras' correction divides by -eps).  Channel
+ * sums run in a fixed order without float atomics (bit-identical run to run).
+ * M <= M3D_BN_TRAIN_FEW_ROWS_MAX: one launch, a workgroup owns a 16-channel
+ * strip and makes every pass (the classifier head's few hundred ROIs);
+ * above: per-row-block partials in the workspace, folded in block order (the
+ * mask head's ROI voxels).  workspace: m3d_bn_train_workspace_bytes(M, C)
+ * bytes (covers either call; 0 in the few-rows regime). */
+#define M3D_BN_TRAIN_FEW_ROWS_MAX 2048
+int64_t m3d_bn_train_few_rows_max(void);
+size_t m3d_bn_train_workspace_bytes(int64_t M, int64_t C);
+int m3d_bn_train_fwd(const float* z, int64_t M, int64_t C, const float* gamma, const float* beta, float eps,
+                     float momentum, int32_t relu, float* y, float* save_mean, float* save_rstd,
+                     float* moving_mean, float* moving_variance, void* workspace, size_t ws_bytes, m3d_stream_t s);
+int m3d_bn_train_bwd(const float* dy, const float* y, const float* z, int64_t M, int64_t C, const float* gamma,
+                     const float* save_mean, const float* save_rstd, int32_t relu, float* dz, float* dgamma,
+                     float* dbeta, void* workspace, size_t ws_bytes, m3d_stream_t s);
 /* Column sums of up to M3D_COL_SUMS_MAX row-major [M, C] matrices in two
  * launches: out[c] += sum_m x[m*C + c] per item -- the bias gradients of the
  * bias-only conv units (tf.nn.bias_add's gradient; the FPN's fpn_c*p* /
