@@ -910,15 +910,22 @@ __global__ __launch_bounds__(256, BK == 64 ? 1 : (NBUF == 1 && !FBN ? 3 : 2)) vo
 // part[split][batch][K][N] of the registered scratch and wg_reduce_kernel adds
 // the splits to C in split order; with a single split (the scratch too small
 // for two), the one writer of each element adds to C without an atomic.
+// Store (either mode): the caller declared C uninitialised scratch (`fresh`,
+// the Winograd-domain dW_hat) and the launcher settled on one split of a
+// non-stream-K grid, so each (batch, k, n) has exactly one writer, which
+// stores its sum: no zero-fill before the launch and no read of C
+// (wg_settle).  Every other fresh launch is preceded by the fill.
 // -------------------------------------------------------------------------
 struct WgOut {
     float* part;
     int64_t pstride;      // floats per split (nbatch * K * N)
     int plain;
+    int store;
 };
 
 __device__ __forceinline__ void wg_put(const WgOut& o, float* C, float* P, int64_t idx, float v) {
     if (P) P[idx] = v;
+    else if (o.store) C[idx] = v;
     else if (o.plain) C[idx] += v;
     else unsafeAtomicAdd(C + idx, v);
 }
@@ -938,7 +945,7 @@ __global__ __launch_bounds__(256) void wg_reduce_kernel(const float* __restrict_
 // deterministic-mode target for `splits` m-splits of an nbatch x K x N gradient
 // (splits may be lowered to what the scratch holds)
 static WgOut wg_out(int64_t& splits, int64_t nbatch, int64_t K, int64_t N) {
-    WgOut o{nullptr, 0, 0};
+    WgOut o{nullptr, 0, 0, 0};
     const DetState d = det();
     if (!d.on) return o;
     const int64_t per = nbatch * K * N;
@@ -959,6 +966,21 @@ static void wg_finish(const WgOut& o, int64_t splits, int64_t nbatch, int64_t K,
     if (!o.part) return;
     hipLaunchKernelGGL(wg_reduce_kernel, dim3(grid_for(o.pstride, 256)), dim3(256), 0, s, o.part, (int)splits,
                        o.pstride, K * N, nbatch > 1 ? bsc : K * N, C);
+}
+
+// `fresh`: C (nbatch contiguous K x N items) holds no prior value.  Called
+// once the launcher knows its final split count: a single split outside the
+// deterministic partials becomes the owner store, every accumulating form
+// (stream-K, m-splits with atomics, partials + wg_reduce_kernel) gets C
+// zero-filled first; returns the fill's status.
+static hipError_t wg_settle(WgOut& o, int64_t splits, bool fresh, float* C, int64_t nbatch, int64_t K, int64_t N,
+                            hipStream_t s) {
+    if (!fresh) return hipSuccess;
+    if (splits == 1 && !o.part) {
+        o.store = 1;
+        return hipSuccess;
+    }
+    return hipMemsetAsync(C, 0, sizeof(float) * (size_t)(nbatch * K * N), s);
 }
 
 // -------------------------------------------------------------------------
@@ -1264,22 +1286,26 @@ static int wgrad_minm_env() {
 }
 
 template <int BI, int BJ, int WI, int WJ, bool AVEC, bool HALO = false>
-static void launch_wgrad(const ConvP& p, const float* dz, float* dw, hipStream_t s, int nbatch = 1) {
+static int launch_wgrad(const ConvP& p, const float* dz, float* dw, hipStream_t s, int nbatch = 1,
+                        bool fresh = false) {     // fresh, return value: as launch_wgrad_x3
     const int64_t tiles = (int64_t)((p.K + BI - 1) / BI) * ((p.N + BJ - 1) / BJ) * nbatch;
     int64_t splits = (1024 + tiles - 1) / tiles;                   // aim >= 1024 blocks
     int64_t minm = wgrad_minm_env() > 32 ? wgrad_minm_env() : 32;
     const int64_t max_splits = (p.M + minm - 1) / minm;             // >= minm m per block
     if (splits > max_splits) splits = max_splits;
     if (splits < 1) splits = 1;
-    const WgOut wo = wg_out(splits, nbatch, p.K, p.N);
+    WgOut wo = wg_out(splits, nbatch, p.K, p.N);
     int64_t mper = (p.M + splits - 1) / splits;
     mper = (mper + 31) / 32 * 32;
     splits = (p.M + mper - 1) / mper;
+    const hipError_t fe = wg_settle(wo, splits, fresh, dw, nbatch, p.K, p.N, s);
+    if (fe != hipSuccess) return (int)fe;
     dim3 grid((unsigned)((p.K + BI - 1) / BI), (unsigned)((p.N + BJ - 1) / BJ),
               (unsigned)(splits * nbatch));
     hipLaunchKernelGGL((conv_wgrad_kernel<BI, BJ, WI, WJ, AVEC, HALO>), grid, dim3(256), 0, s, p, dz, dw,
                        mper, wo);
     wg_finish(wo, splits, nbatch, p.K, p.N, p.bsy, dw, s);
+    return 0;
 }
 
 
@@ -1778,8 +1804,8 @@ static int wgrad_tr_env() {
     return v;
 }
 
-static void launch_wgrad_tr(const float* A, const float* Bm, float* C, int64_t M, int K, int N, int nbatch,
-                            int64_t bsa, int64_t bsb, int64_t bsc, hipStream_t s) {
+static int launch_wgrad_tr(const float* A, const float* Bm, float* C, int64_t M, int K, int N, int nbatch,
+                           int64_t bsa, int64_t bsb, int64_t bsc, hipStream_t s, bool fresh) {
     const int64_t tiles = (int64_t)((K + 255) / 256) * ((N + 255) / 256) * nbatch;
     const int64_t cus = num_cus();
     static constexpr int64_t minm = M3D_TUNE_X3W_TR_MINM;
@@ -1797,9 +1823,13 @@ static void launch_wgrad_tr(const float* A, const float* Bm, float* C, int64_t M
         if (G > cus) G = cus;
         G = G / sk.tn * sk.tn;                        // whole groups of the tn column tiles
         if (G < sk.tn) G = sk.tn;
+        WgOut wo{nullptr, 0, 0, 0};
+        // a tile's steps may span two workgroups: stream-K always accumulates (never the owner store)
+        const hipError_t fe = wg_settle(wo, 2, fresh, C, nbatch, K, N, s);
+        if (fe != hipSuccess) return (int)fe;
         hipLaunchKernelGGL((x3_wgrad_tr_kernel<0, true>), dim3((unsigned)G), dim3(512), 0, s, A, Bm, C, M, K, N,
-                           (int64_t)0, bsa, bsb, bsc, WgOut{nullptr, 0, 0}, sk);
-        return;
+                           (int64_t)0, bsa, bsb, bsc, wo, sk);
+        return 0;
     }
     int64_t splits = (cus + tiles - 1) / tiles;
     // M3D_X3W_TR_MINM: fewest m rows per workgroup.  Every split adds a 256x256
@@ -1811,26 +1841,30 @@ static void launch_wgrad_tr(const float* A, const float* Bm, float* C, int64_t M
     const int64_t max_splits = (M + minm - 1) / minm;
     if (splits > max_splits) splits = max_splits;
     if (splits < 1) splits = 1;
-    const WgOut wo = wg_out(splits, nbatch, K, N);
+    WgOut wo = wg_out(splits, nbatch, K, N);
     int64_t mper = (M + splits - 1) / splits;
     mper = (mper + W2_BK - 1) / W2_BK * W2_BK;
     splits = (M + mper - 1) / mper;
+    const hipError_t fe = wg_settle(wo, splits, fresh, C, nbatch, K, N, s);
+    if (fe != hipSuccess) return (int)fe;
     dim3 grid((unsigned)((K + 255) / 256), (unsigned)((N + 255) / 256), (unsigned)(splits * nbatch));
     hipLaunchKernelGGL(x3_wgrad_tr_kernel<0>, grid, dim3(512), 0, s, A, Bm, C, M, K, N, mper, bsa, bsb, bsc, wo,
                        X3wSK{});
     wg_finish(wo, splits, nbatch, K, N, bsc, C, s);
+    return 0;
 }
 
 // M3D_GEMM_X3 bit 2: the batched Winograd weight-gradient GEMMs on x3_wgrad_kernel
 static int wgrad_x3_env() { return (x3_mask() >> 2) & 1; }
 
-// C[b] += A[b]^T B[b]: A [M][K], B [M][N], C [K][N], batch strides bsa/bsb/bsc
-static void launch_wgrad_x3(const float* A, const float* Bm, float* C, int64_t M, int K, int N, int nbatch,
-                            int64_t bsa, int64_t bsb, int64_t bsc, hipStream_t s) {
-    if (wgrad_tr_env() && K >= 192 && N >= 192) {
-        launch_wgrad_tr(A, Bm, C, M, K, N, nbatch, bsa, bsb, bsc, s);
-        return;
-    }
+// C[b] += A[b]^T B[b]: A [M][K], B [M][N], C [K][N], batch strides bsa/bsb/bsc.
+// fresh: C is uninitialised scratch (nbatch contiguous items, bsc = K * N) and
+// the result is C[b] = A[b]^T B[b]: owner store or zero-fill, see wg_settle.
+// Returns 0, or the hipError_t of a failed zero-fill (fresh only).
+static int launch_wgrad_x3(const float* A, const float* Bm, float* C, int64_t M, int K, int N, int nbatch,
+                           int64_t bsa, int64_t bsb, int64_t bsc, hipStream_t s, bool fresh = false) {
+    if (wgrad_tr_env() && K >= 192 && N >= 192)
+        return launch_wgrad_tr(A, Bm, C, M, K, N, nbatch, bsa, bsb, bsc, s, fresh);
     if (K <= 64 || N <= 64) {          // x3_wgrad64_kernel: 64x64 tiles, the m chunk over the waves
         const int64_t tiles = (int64_t)((K + 63) / 64) * ((N + 63) / 64);
         int64_t splits = (1024 + tiles * nbatch - 1) / (tiles * nbatch);
@@ -1838,14 +1872,16 @@ static void launch_wgrad_x3(const float* A, const float* Bm, float* C, int64_t M
         const int64_t max_splits = (M + minm - 1) / minm;
         if (splits > max_splits) splits = max_splits;
         if (splits < 1) splits = 1;
-        const WgOut wo = wg_out(splits, nbatch, K, N);
+        WgOut wo = wg_out(splits, nbatch, K, N);
         int64_t mper = (M + splits - 1) / splits;
         mper = (mper + 63) / 64 * 64;
         splits = (M + mper - 1) / mper;
+        const hipError_t fe = wg_settle(wo, splits, fresh, C, nbatch, K, N, s);
+        if (fe != hipSuccess) return (int)fe;
         hipLaunchKernelGGL((x3_wgrad64_kernel<2>), dim3((unsigned)(tiles * splits * nbatch)), dim3(256), 0, s, A, Bm, C, M,
                            K, N, mper, bsa, bsb, bsc, wo);
         wg_finish(wo, splits, nbatch, K, N, bsc, C, s);
-        return;
+        return 0;
     }
     const int64_t tiles = (int64_t)((K + 127) / 128) * ((N + 127) / 128) * nbatch;
     int64_t splits = (1024 + tiles - 1) / tiles;
@@ -1853,14 +1889,17 @@ static void launch_wgrad_x3(const float* A, const float* Bm, float* C, int64_t M
     const int64_t max_splits = (M + minm - 1) / minm;
     if (splits > max_splits) splits = max_splits;
     if (splits < 1) splits = 1;
-    const WgOut wo = wg_out(splits, nbatch, K, N);
+    WgOut wo = wg_out(splits, nbatch, K, N);
     int64_t mper = (M + splits - 1) / splits;
     mper = (mper + 31) / 32 * 32;
     splits = (M + mper - 1) / mper;
+    const hipError_t fe = wg_settle(wo, splits, fresh, C, nbatch, K, N, s);
+    if (fe != hipSuccess) return (int)fe;
     dim3 grid((unsigned)((K + 127) / 128), (unsigned)((N + 127) / 128), (unsigned)(splits * nbatch));
     // 2 blocks/CU (3 at 164 VGPRs: faster alone, step unchanged)
     hipLaunchKernelGGL((x3_wgrad_kernel<2>), grid, dim3(256), 0, s, A, Bm, C, M, K, N, mper, bsa, bsb, bsc, wo);
     wg_finish(wo, splits, nbatch, K, N, bsc, C, s);
+    return 0;
 }
 
 // =========================================================================
@@ -5004,8 +5043,8 @@ static int bwd_weight_wino(const float* x, const float* u_in, const float* dz, i
     WinoGeom g = wino_geom(B, H, W, OD, D, pz, nz);
     g.halo = halo; g.hlo = hlo; g.hhi = hhi;
     WinoWs ws = wino_ws(workspace, g, Cin, Cout, nz);   // V <- dW_hat, U <- B^T x, M <- A dz
-    if (hipMemsetAsync(ws.V, 0, sizeof(float) * wino_points(nz) * (size_t)Cin * Cout, st(s)) != hipSuccess)
-        return check_launch("memset dW_hat");
+    // dW_hat is uninitialised scratch: the GEMM launcher stores into it where a
+    // single workgroup owns each tile, and zero-fills it first where it accumulates
     if (u_in)
         ws.U = const_cast<float*>(u_in);       // the forward's transformed input, kept
     else
@@ -5014,15 +5053,20 @@ static int bwd_weight_wino(const float* x, const float* u_in, const float* dz, i
         WINO_LAUNCH_NZ(nz, wino_grad_kernel, dim3(grid_for(g.T * Cout, 256)), dim3(256), 0, st(s), dz, g,
                        (int)Cout, ws.M);
     // (Cin, Cout <= 64: x3_wgrad64_kernel, the whole 64x64 product per workgroup)
+    int fe = 0;                 // the hipError_t of a failed zero-fill
     if (wgrad_x3_env() && (Cout > 64 || Cin <= 64)) {
-        launch_wgrad_x3(ws.U, ws.M, ws.V, g.T, (int)Cin, (int)Cout, wino_points(nz), g.T * Cin, g.T * Cout,
-                        (int64_t)Cin * Cout, st(s));
+        fe = launch_wgrad_x3(ws.U, ws.M, ws.V, g.T, (int)Cin, (int)Cout, wino_points(nz), g.T * Cin, g.T * Cout,
+                             (int64_t)Cin * Cout, st(s), true);
     } else {
         ConvP p = wino_gemm_p(ws.U, g.T, (int)Cin, nullptr, (int)Cout);
         p.bsw = g.T * Cout;                 // dz (DY) batch stride
         p.bsy = (int64_t)Cin * Cout;        // dW_hat batch stride
-        if (Cout <= 64) launch_wgrad<128, 64, 2, 2, true>(p, ws.M, ws.V, st(s), wino_points(nz));
-        else launch_wgrad<128, 128, 2, 2, true>(p, ws.M, ws.V, st(s), wino_points(nz));
+        if (Cout <= 64) fe = launch_wgrad<128, 64, 2, 2, true>(p, ws.M, ws.V, st(s), wino_points(nz), true);
+        else fe = launch_wgrad<128, 128, 2, 2, true>(p, ws.M, ws.V, st(s), wino_points(nz), true);
+    }
+    if (fe) {
+        set_error("memset dW_hat: %s", hipGetErrorString((hipError_t)fe));
+        return M3D_EHIP;
     }
     WINO_LAUNCH_NZ(nz, wino_wgrad_out_kernel, dim3(grid_for(Cin * Cout, 256)), dim3(256), 0, st(s),
                        ws.V, (int)Cin, (int)Cout, dw);
