@@ -47,7 +47,7 @@ struct ConvP {
     // batched GEMMs (Winograd points): blockIdx.z selects the batch; A, W and Y
     // advance by these element strides (0 for ordinary convs)
     int64_t bsa, bsw, bsy;
-    int dly = 1, dlx = 1, dlz = 1;   // dilation (fwd only; mrcnn_mask_conv3b)
+    int dly = 1, dlx = 1, dlz = 1;   // dilation (mrcnn_mask_conv3b: fwd, bwd-data on the flipped taps, bwd-weight)
     int nbatch = 1;                  // batches (PERSIST: looped inside the grid)
     // depth-slab halo planes beside the slab (the stem and the direct weight
     // gradient, m3d_conv3d_*_halo): the conv runs on the virtual z grid
@@ -1040,7 +1040,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(ConvP p, const float
     if (kok) {
         const int tap = kcol / p.C;
         cc = kcol - tap * p.C;
-        ky = tap / taps_kwkd; kx = (tap / taps_kd) % p.kw; kz = tap % taps_kd;
+        ky = tap / taps_kwkd * p.dly; kx = (tap / taps_kd) % p.kw * p.dlx; kz = tap % taps_kd * p.dlz;
     }
     constexpr int GC = BJ / 4;
     const int gcol = tid % GC, grow0 = tid / GC;
@@ -3851,7 +3851,8 @@ extern "C" int m3d_conv3d_fwd(const float* x, int64_t B, int64_t H, int64_t W, i
 static int bwd_data_direct(const float* dz, const float* w, int64_t B, int64_t H, int64_t W, int64_t D, int64_t Cin,
                            int32_t kh, int32_t kw, int32_t kd, int64_t Cout, int64_t OH, int64_t OW, int64_t OD,
                            int32_t sy, int32_t sx, int32_t sz, int32_t py, int32_t px, int32_t pz, float* dx,
-                           int32_t accumulate, hipStream_t s, const Epi* fb, int64_t* fb_rows);
+                           int32_t accumulate, hipStream_t s, const Epi* fb, int64_t* fb_rows, int32_t dly = 1,
+                           int32_t dlx = 1, int32_t dlz = 1);
 
 extern "C" int m3d_conv3d_bwd_data(const float* dz, const float* w, int64_t B, int64_t H,
                                    int64_t W, int64_t D, int64_t Cin, int32_t kh, int32_t kw,
@@ -3860,6 +3861,20 @@ extern "C" int m3d_conv3d_bwd_data(const float* dz, const float* w, int64_t B, i
                                    int32_t pz, float* dx, int32_t accumulate, m3d_stream_t s) {
     return bwd_data_direct(dz, w, B, H, W, D, Cin, kh, kw, kd, Cout, OH, OW, OD, sy, sx, sz, py, px, pz, dx,
                            accumulate, st(s), nullptr, nullptr);
+}
+
+// The data gradient of a stride-1 dilated conv (mrcnn_mask_conv3b, core/models.py:1215-1218): the
+// same implicit GEMM over dz on the flipped taps, stepped by the dilation, with pad' = dl*(k-1) - pad.
+extern "C" int m3d_conv3d_bwd_data_dil(const float* dz, const float* w, int64_t B, int64_t H, int64_t W,
+                                       int64_t D, int64_t Cin, int32_t kh, int32_t kw, int32_t kd,
+                                       int64_t Cout, int64_t OH, int64_t OW, int64_t OD, int32_t sy,
+                                       int32_t sx, int32_t sz, int32_t py, int32_t px, int32_t pz,
+                                       int32_t dly, int32_t dlx, int32_t dlz, float* dx,
+                                       int32_t accumulate, m3d_stream_t s) {
+    if (sy != 1 || sx != 1 || sz != 1) return einval("conv3d bwd-data (dilated): stride must be 1");
+    if (accumulate != 0 && accumulate != 1) return einval("conv3d bwd-data (dilated): accumulate must be 0 or 1");
+    return bwd_data_direct(dz, w, B, H, W, D, Cin, kh, kw, kd, Cout, OH, OW, OD, sy, sx, sz, py, px, pz, dx,
+                           accumulate, st(s), nullptr, nullptr, dly, dlx, dlz);
 }
 
 // the output-tile height dispatch_gemm picks for a GEMM of N columns (rows of
@@ -3873,9 +3888,13 @@ static int dispatch_bm(const ConvP& p, int nbatch = 1) {
 static int bwd_data_direct(const float* dz, const float* w, int64_t B, int64_t H, int64_t W, int64_t D, int64_t Cin,
                            int32_t kh, int32_t kw, int32_t kd, int64_t Cout, int64_t OH, int64_t OW, int64_t OD,
                            int32_t sy, int32_t sx, int32_t sz, int32_t py, int32_t px, int32_t pz, float* dx,
-                           int32_t accumulate, hipStream_t hs, const Epi* fb, int64_t* fb_rows) {
+                           int32_t accumulate, hipStream_t hs, const Epi* fb, int64_t* fb_rows, int32_t dly,
+                           int32_t dlx, int32_t dlz) {
     int rc = conv_check(B, H, W, D, Cin, kh, kw, kd, Cout, OH, OW, OD, sy, sx, sz);
     if (rc) return rc;
+    if (dly <= 0 || dlx <= 0 || dlz <= 0) return einval("conv3d bwd-data: dilation must be positive");
+    if ((dly != 1 || dlx != 1 || dlz != 1) && (sy != 1 || sx != 1 || sz != 1))
+        return einval("conv3d bwd-data: dilated convs supported at stride 1 only");
     if (Cout % 32) return einval("conv3d bwd-data: Cout must be a multiple of 32");
     if (Cin % 4) return einval("conv3d bwd-data: Cin must be a multiple of 4");
     const bool unit = kh == 1 && kw == 1 && kd == 1;
@@ -3885,7 +3904,8 @@ static int bwd_data_direct(const float* dz, const float* w, int64_t B, int64_t H
         if (fb) return einval("conv3d bwd-data (fused BN backward): batch past the 32-bit operand bound");
         for (int64_t b = 0; b < B; ++b) {
             rc = bwd_data_direct(dz + b * OH * OW * OD * Cout, w, 1, H, W, D, Cin, kh, kw, kd, Cout, OH, OW, OD,
-                                 sy, sx, sz, py, px, pz, dx + b * H * W * D * Cin, accumulate, hs, nullptr, nullptr);
+                                 sy, sx, sz, py, px, pz, dx + b * H * W * D * Cin, accumulate, hs, nullptr, nullptr,
+                                 dly, dlx, dlz);
             if (rc) return rc;
         }
         return M3D_OK;
@@ -3915,11 +3935,12 @@ static int bwd_data_direct(const float* dz, const float* w, int64_t B, int64_t H
         e.simple = (sy == 1 && sx == 1 && sz == 1 && H == OH && W == OW && D == OD);
         if (py || px || pz) return einval("conv3d bwd-data: 1x1x1 conv with padding unsupported");
     } else {
-        // M grid = dx grid; A = dz with pad' = k-1-p, flipped taps
+        // M grid = dx grid; A = dz with pad' = dl*(k-1)-p, flipped taps at the conv's dilation
         p.H = (int)OH; p.W = (int)OW; p.D = (int)OD;
         p.OH = (int)H; p.OW = (int)W; p.OD = (int)D;
         p.sy = p.sx = p.sz = 1;
-        p.py = kh - 1 - py; p.px = kw - 1 - px; p.pz = kd - 1 - pz;
+        p.dly = dly; p.dlx = dlx; p.dlz = dlz;
+        p.py = dly * (kh - 1) - py; p.px = dlx * (kw - 1) - px; p.pz = dlz * (kd - 1) - pz;
         e.YH = (int)H; e.YW = (int)W; e.YD = (int)D;
         e.ysy = e.ysx = e.ysz = 1;
         e.simple = 1;
@@ -4154,18 +4175,23 @@ extern "C" int m3d_conv3d_bwd_data_splitk_bn(const float* dz, const float* w, in
                              bn_ws_bytes, st(s));
 }
 
-extern "C" int m3d_conv3d_bwd_weight(const float* x, const float* dz, int64_t B, int64_t H,
-                                     int64_t W, int64_t D, int64_t Cin, int32_t kh, int32_t kw,
-                                     int32_t kd, int64_t Cout, int64_t OH, int64_t OW, int64_t OD,
-                                     int32_t sy, int32_t sx, int32_t sz, int32_t py, int32_t px,
-                                     int32_t pz, float* dw, const m3d_det_t* det, m3d_stream_t s) {
+// The weight gradient with the conv's dilation on the im2col taps (mrcnn_mask_conv3b,
+// core/models.py:1215-1218); dilation 1 is m3d_conv3d_bwd_weight.
+extern "C" int m3d_conv3d_bwd_weight_dil(const float* x, const float* dz, int64_t B, int64_t H,
+                                         int64_t W, int64_t D, int64_t Cin, int32_t kh, int32_t kw,
+                                         int32_t kd, int64_t Cout, int64_t OH, int64_t OW, int64_t OD,
+                                         int32_t sy, int32_t sx, int32_t sz, int32_t py, int32_t px,
+                                         int32_t pz, int32_t dly, int32_t dlx, int32_t dlz, float* dw,
+                                         const m3d_det_t* det, m3d_stream_t s) {
     M3D_DET_SCOPE(det);
     int rc = conv_check(B, H, W, D, Cin, kh, kw, kd, Cout, OH, OW, OD, sy, sx, sz);
     if (rc) return rc;
+    if (dly <= 0 || dlx <= 0 || dlz <= 0) return einval("conv3d bwd-weight: dilation must be positive");
     if (per_item(B, H * W * D, Cin, OH * OW * OD, Cout)) {      // dw accumulates over the items
         for (int64_t b = 0; b < B; ++b) {
-            rc = m3d_conv3d_bwd_weight(x + b * H * W * D * Cin, dz + b * OH * OW * OD * Cout, 1, H, W, D, Cin, kh,
-                                       kw, kd, Cout, OH, OW, OD, sy, sx, sz, py, px, pz, dw, det, s);
+            rc = m3d_conv3d_bwd_weight_dil(x + b * H * W * D * Cin, dz + b * OH * OW * OD * Cout, 1, H, W, D, Cin,
+                                           kh, kw, kd, Cout, OH, OW, OD, sy, sx, sz, py, px, pz, dly, dlx, dlz,
+                                           dw, det, s);
             if (rc) return rc;
         }
         return M3D_OK;
@@ -4173,8 +4199,9 @@ extern "C" int m3d_conv3d_bwd_weight(const float* x, const float* dz, int64_t B,
     ConvP p{x, (int)B, (int)H, (int)W, (int)D, (int)Cin, (int)OH, (int)OW, (int)OD, kh, kw, kd,
             sy, sx, sz, py, px, pz, B * OH * OW * OD, (int)(kh * kw * kd * Cin), nullptr,
             (int)Cout, 0, 0, 0, 0};
+    p.dly = dly; p.dlx = dlx; p.dlz = dlz;
     const bool vec = (Cin % 4) == 0;
-    if (stem_ok(Cin, kh, kw, kd, Cout, sy, sx, sz, 1, 1, 1, 0, 0, 0))
+    if (stem_ok(Cin, kh, kw, kd, Cout, sy, sx, sz, dly, dlx, dlz, 0, 0, 0))
         return launch_stem_wgrad(p, dz, dw, st(s));
     // 1x1x1 stride-1 convs: im2col is x itself, the plain weight-gradient GEMM
     // dW += x^T dz -- on the exact bf16 split like the Winograd ones
@@ -4196,6 +4223,45 @@ extern "C" int m3d_conv3d_bwd_weight(const float* x, const float* dz, int64_t B,
         else launch_wgrad<128, 128, 2, 2, false>(p, dz, dw, st(s));
     }
     return check_launch("conv_wgrad_kernel");
+}
+
+extern "C" int m3d_conv3d_bwd_weight(const float* x, const float* dz, int64_t B, int64_t H,
+                                     int64_t W, int64_t D, int64_t Cin, int32_t kh, int32_t kw,
+                                     int32_t kd, int64_t Cout, int64_t OH, int64_t OW, int64_t OD,
+                                     int32_t sy, int32_t sx, int32_t sz, int32_t py, int32_t px,
+                                     int32_t pz, float* dw, const m3d_det_t* det, m3d_stream_t s) {
+    return m3d_conv3d_bwd_weight_dil(x, dz, B, H, W, D, Cin, kh, kw, kd, Cout, OH, OW, OD, sy, sx, sz, py, px, pz,
+                                     1, 1, 1, dw, det, s);
+}
+
+// ---- backward of the 2x2x2 stride-2 transposed conv (m3d_deconv3d_k2s2) --------
+// y[2i+t, o] = sum_c x[i, c] w[t, o, c]: the Keras kernel [2,2,2,Cout,Cin] read as
+// a CONV kernel [2,2,2, Cin' = Cout, Cout' = Cin] (the same buffer) makes
+//   dx = the 2^3 stride-2 'valid' conv of g with it    (the forward implicit GEMM)
+//   dw = that conv's weight gradient with x' = g, dz' = x  (conv_wgrad_kernel,
+//        whose im2col coordinates carry any kernel size and stride)
+static int deconv_bwd_check(int64_t B, int64_t H, int64_t W, int64_t D, int64_t Cin, int64_t Cout) {
+    if (B <= 0 || H <= 0 || W <= 0 || D <= 0 || Cin <= 0 || Cout <= 0)
+        return einval("deconv3d bwd: tensor dimensions must be positive");
+    if (Cout % 4 || Cin % 4) return einval("deconv3d bwd: Cin % 4 == 0 and Cout % 4 == 0 required");
+    return M3D_OK;
+}
+
+extern "C" int m3d_deconv3d_k2s2_bwd_data(const float* g, const float* w, int64_t B, int64_t H, int64_t W,
+                                          int64_t D, int64_t Cin, int64_t Cout, float* dx, m3d_stream_t s) {
+    const int rc = deconv_bwd_check(B, H, W, D, Cin, Cout);
+    if (rc) return rc;
+    return m3d_conv3d_fwd_dil(g, B, 2 * H, 2 * W, 2 * D, Cout, w, 2, 2, 2, Cin, H, W, D, 2, 2, 2, 0, 0, 0, 1, 1, 1,
+                              nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, dx, Cin, nullptr, 0, 0, s);
+}
+
+extern "C" int m3d_deconv3d_k2s2_bwd_weight(const float* x, const float* g, int64_t B, int64_t H, int64_t W,
+                                            int64_t D, int64_t Cin, int64_t Cout, float* dw, const m3d_det_t* det,
+                                            m3d_stream_t s) {
+    const int rc = deconv_bwd_check(B, H, W, D, Cin, Cout);
+    if (rc) return rc;
+    return m3d_conv3d_bwd_weight_dil(g, x, B, 2 * H, 2 * W, 2 * D, Cout, 2, 2, 2, Cin, H, W, D, 2, 2, 2, 0, 0, 0,
+                                     1, 1, 1, dw, det, s);
 }
 
 // ---- depth-slab forms of the direct convs: halo planes beside the slab ---------

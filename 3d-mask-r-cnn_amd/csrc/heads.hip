@@ -14,6 +14,11 @@
 //                         (core/utils.py:412-458), clip, min size
 //   detections_kernel     NMS gather, re-normalise, [max_inst, 8] rows, zero pad
 //                         (core/models.py:1503-1524)
+//   mask_out_bwd_kernel + mask_out_fold_kernel  backward of mrcnn_mask (1^3 conv,
+//                         sigmoid) joined with mrcnn_mask_deconv's ReLU
+//                         (core/models.py:1229-1237): g_up and three parameter
+//                         gradients in one HBM pass, ordered partial sums
+//   add4_kernel           KL.Add of mrcnn_mask_res3 in training mode (core/models.py:1222)
 // Compiled with -ffp-contract=off like the other exact-order kernels.
 #include <float.h>
 
@@ -151,9 +156,220 @@ __global__ void detections_kernel(const float* __restrict__ boxes_px,
     o[7] = scores[i];
 }
 
+// ---- backward of mrcnn_mask (1^3 conv ch -> C, sigmoid) joined with the ReLU of
+// mrcnn_mask_deconv (core/models.py:1229-1237) ---------------------------------
+// A rank-C update (C = 2 in the reference) over V = T (2p)^3 rows of ch channels:
+// HBM-bound, up read once and g_up written once.  A workgroup owns a contiguous
+// run of `rpb` rows (a multiple of MOB_TILE) and walks it in tiles of MOB_TILE
+// rows:
+//   phase A: thread t forms gl[v][k] = g_mask out (1 - out) of row v = tile + t
+//            into LDS and adds it to its running db[k];
+//   phase B: TPR = 2^ceil(log2(ch/4)) threads span a row (one float4 of channels
+//            each, held for the whole kernel: its 4 x C weights stay in
+//            registers), 256 / TPR rows per pass: g_up = (gl . w[c]) (up > 0)
+//            stored, dW[c][k] += up gl[k] and dbd[c] += g_up in registers.
+// At the end the row groups' registers are summed through LDS in row-group
+// order and the workgroup writes one row of partials [ch*C dW | ch dbd | C db];
+// mask_out_fold_kernel adds the rows to the three gradients in workgroup order
+// (16 slices of consecutive workgroups, then the slices in order).  No atomics:
+// the result depends on V, ch and C alone.  CT = 2: the reference's class
+// count, unrolled; CT = 8: any C <= 8 (a runtime bound inside the unrolled loops).
+// All addresses are 64-bit (no buffer descriptors): no 4 GiB operand bound.
+constexpr int MOB_TILE = 256;
+constexpr int MOB_FOLD_E = 16, MOB_FOLD_S = 16;
+
+template <int CT>
+__global__ __launch_bounds__(256) void mask_out_bwd_kernel(const float* __restrict__ g_mask,
+                                                           const float* __restrict__ out,
+                                                           const float* __restrict__ up,
+                                                           const float* __restrict__ w, int64_t V, int ch, int C,
+                                                           int tpr, int64_t rpb, float* __restrict__ g_up,
+                                                           float* __restrict__ part) {
+    __shared__ float sgl[MOB_TILE * CT];
+    __shared__ __attribute__((aligned(16))) float red[1024 * (CT + 1)];
+    const int tid = threadIdx.x;
+    const int q = tid % tpr, rg = tid / tpr, nrg = 256 / tpr;
+    const int L4 = ch >> 2;
+    const bool qok = q < L4;
+    const int64_t v_begin = (int64_t)blockIdx.x * rpb;
+    const int64_t v_end = v_begin + rpb < V ? v_begin + rpb : V;
+    float wr[4][CT];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int k = 0; k < CT; ++k) wr[j][k] = (qok && k < C) ? w[(int64_t)(4 * q + j) * C + k] : 0.0f;
+    float dwa[4][CT], dba[4], dbk[CT];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        dba[j] = 0.0f;
+#pragma unroll
+        for (int k = 0; k < CT; ++k) dwa[j][k] = 0.0f;
+    }
+#pragma unroll
+    for (int k = 0; k < CT; ++k) dbk[k] = 0.0f;
+    for (int64_t t0 = v_begin; t0 < v_end; t0 += MOB_TILE) {
+        {
+            const int64_t v = t0 + tid;
+#pragma unroll
+            for (int k = 0; k < CT; ++k) {
+                float gl = 0.0f;
+                if (v < v_end && k < C) {
+                    const float o = out[v * C + k];
+                    gl = g_mask[v * C + k] * o * (1.0f - o);
+                }
+                sgl[tid * CT + k] = gl;
+                dbk[k] += gl;
+            }
+        }
+        __syncthreads();
+        const int rows = (int)(v_end - t0 < MOB_TILE ? v_end - t0 : MOB_TILE);
+        if (qok) {
+#pragma unroll 4
+            for (int r = rg; r < rows; r += nrg) {
+                const int64_t off = (t0 + r) * ch + 4 * q;
+                const float4 u = *reinterpret_cast<const float4*>(up + off);
+                float gl[CT];
+#pragma unroll
+                for (int k = 0; k < CT; ++k) gl[k] = sgl[r * CT + k];
+                const float uu[4] = {u.x, u.y, u.z, u.w};
+                float gg[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float s = 0.0f;
+#pragma unroll
+                    for (int k = 0; k < CT; ++k) {
+                        s += gl[k] * wr[j][k];
+                        dwa[j][k] += uu[j] * gl[k];
+                    }
+                    gg[j] = uu[j] > 0.0f ? s : 0.0f;
+                    dba[j] += gg[j];
+                }
+                *reinterpret_cast<float4*>(g_up + off) = make_float4(gg[0], gg[1], gg[2], gg[3]);
+            }
+        }
+        __syncthreads();
+    }
+    // fold the row groups (fixed order) and the 256 db rows; one partial row per workgroup
+    const int nE = ch * (CT + 1);                 // per row group: [c][k < CT | dbd]
+    if (qok) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+#pragma unroll
+            for (int k = 0; k < CT; ++k) red[rg * nE + (4 * q + j) * (CT + 1) + k] = dwa[j][k];
+            red[rg * nE + (4 * q + j) * (CT + 1) + CT] = dba[j];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < CT; ++k) sgl[tid * CT + k] = dbk[k];
+    __syncthreads();
+    float* prow = part + (int64_t)blockIdx.x * ((int64_t)ch * C + ch + C);
+    for (int e = tid; e < nE; e += 256) {
+        const int c = e / (CT + 1), k = e - c * (CT + 1);
+        float s = red[e];
+        for (int g = 1; g < nrg; ++g) s += red[g * nE + e];
+        if (k == CT) prow[(int64_t)ch * C + c] = s;
+        else if (k < C) prow[(int64_t)c * C + k] = s;
+    }
+    if (tid < C) {
+        float s = 0.0f;
+        for (int t = 0; t < 256; ++t) s += sgl[t * CT + tid];
+        prow[(int64_t)ch * C + ch + tid] = s;
+    }
+}
+
+// dst[e] += sum over workgroup rows of part[row][e]: MOB_FOLD_S slices of
+// consecutive rows summed in row order, then the slices in order.
+// e < ch*C -> dW, < ch*C + ch -> the deconv bias gradient, else db.
+__global__ __launch_bounds__(256) void mask_out_fold_kernel(const float* __restrict__ part, int64_t nrows, int ne,
+                                                            int n_dw, int n_dbd, float* __restrict__ dW,
+                                                            float* __restrict__ dbd, float* __restrict__ db) {
+    __shared__ float red[MOB_FOLD_S][MOB_FOLD_E];
+    const int el = threadIdx.x % MOB_FOLD_E, sl = threadIdx.x / MOB_FOLD_E;
+    const int e = blockIdx.x * MOB_FOLD_E + el;
+    const int64_t per = (nrows + MOB_FOLD_S - 1) / MOB_FOLD_S;
+    const int64_t r0 = sl * per, r1 = r0 + per < nrows ? r0 + per : nrows;
+    float s = 0.0f;
+    if (e < ne)
+        for (int64_t r = r0; r < r1; ++r) s += part[r * ne + e];
+    red[sl][el] = s;
+    __syncthreads();
+    if (sl == 0 && e < ne) {
+        for (int g = 1; g < MOB_FOLD_S; ++g) s += red[g][el];
+        if (e < n_dw) dW[e] += s;
+        else if (e < n_dw + n_dbd) dbd[e - n_dw] += s;
+        else db[e - n_dw - n_dbd] += s;
+    }
+}
+
+// KL.Add of two activated branches (mrcnn_mask_res3, core/models.py:1222) where
+// the second comes out of a batch-statistics BN and cannot ride a conv epilogue:
+// out = a + b over n floats (n % 4 == 0), float4 lanes, grid-stride.
+__global__ __launch_bounds__(256) void add4_kernel(const float4* __restrict__ a, const float4* __restrict__ b,
+                                                   float4* __restrict__ out, int64_t n4) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        const float4 x = a[i], y = b[i];
+        out[i] = make_float4(x.x + y.x, x.y + y.y, x.z + y.z, x.w + y.w);
+    }
+}
+
+// rows per workgroup: a function of V alone (the partial sums' grouping is part of the result's bits)
+static int64_t mask_out_rpb(int64_t V) { return V >= ((int64_t)1 << 18) ? 4 * MOB_TILE : MOB_TILE; }
+
 }  // namespace m3d
 
 using namespace m3d;
+
+extern "C" int m3d_add_f32(const float* a, const float* b, float* out, int64_t n, m3d_stream_t s) {
+    if (n < 0 || n % 4) return einval("add_f32: n must be a non-negative multiple of 4");
+    if (n == 0) return M3D_OK;
+    if (!a || !b || !out) return einval("add_f32: null tensor");
+    hipLaunchKernelGGL(add4_kernel, dim3(grid_for(n / 4, 256, 1 << 16)), dim3(256), 0, st(s),
+                       reinterpret_cast<const float4*>(a), reinterpret_cast<const float4*>(b),
+                       reinterpret_cast<float4*>(out), n / 4);
+    return check_launch("add4_kernel");
+}
+
+static int mask_out_check(int64_t V, int64_t ch, int32_t C) {
+    if (V <= 0 || ch <= 0 || C <= 0) return einval("mask_out_bwd: V, ch and C must be positive");
+    if (C > 8) return einval("mask_out_bwd: at most 8 classes");
+    if (ch % 4 || ch > 1024) return einval("mask_out_bwd: ch must be a multiple of 4, at most 1024");
+    if ((V + MOB_TILE - 1) / MOB_TILE > 0x7FFFFFFF) return einval("mask_out_bwd: too many rows");
+    return M3D_OK;
+}
+
+extern "C" size_t m3d_mask_out_bwd_workspace_bytes(int64_t V, int64_t ch, int32_t C) {
+    if (V <= 0 || ch <= 0 || C <= 0 || C > 8 || ch % 4 || ch > 1024) return 0;
+    const int64_t rpb = mask_out_rpb(V);
+    return sizeof(float) * (size_t)((V + rpb - 1) / rpb) * (size_t)(ch * C + ch + C);
+}
+
+extern "C" int m3d_mask_out_bwd(const float* g_mask, const float* out, const float* up, const float* w, int64_t V,
+                                int64_t ch, int32_t C, float* g_up, float* dW, float* db, float* d_deconv_bias,
+                                void* workspace, size_t ws_bytes, m3d_stream_t s) {
+    const int rc = mask_out_check(V, ch, C);
+    if (rc) return rc;
+    if (!g_mask || !out || !up || !w || !g_up || !dW || !db || !d_deconv_bias)
+        return einval("mask_out_bwd: null tensor");
+    if (!workspace || ws_bytes < m3d_mask_out_bwd_workspace_bytes(V, ch, C))
+        return einval("mask_out_bwd: workspace too small (m3d_mask_out_bwd_workspace_bytes)");
+    const int64_t rpb = mask_out_rpb(V);
+    const int64_t nblk = (V + rpb - 1) / rpb;
+    int tpr = 1;
+    while (tpr < ch / 4) tpr <<= 1;
+    float* part = static_cast<float*>(workspace);
+    if (C == 2)
+        hipLaunchKernelGGL(mask_out_bwd_kernel<2>, dim3((unsigned)nblk), dim3(256), 0, st(s), g_mask, out, up, w, V,
+                           (int)ch, (int)C, tpr, rpb, g_up, part);
+    else
+        hipLaunchKernelGGL(mask_out_bwd_kernel<8>, dim3((unsigned)nblk), dim3(256), 0, st(s), g_mask, out, up, w, V,
+                           (int)ch, (int)C, tpr, rpb, g_up, part);
+    int rc2 = check_launch("mask_out_bwd_kernel");
+    if (rc2) return rc2;
+    const int ne = (int)(ch * C + ch + C);
+    hipLaunchKernelGGL(mask_out_fold_kernel, dim3((unsigned)((ne + MOB_FOLD_E - 1) / MOB_FOLD_E)), dim3(256), 0, st(s),
+                       part, nblk, ne, (int)(ch * C), (int)ch, dW, d_deconv_bias, db);
+    return check_launch("mask_out_fold_kernel");
+}
 
 extern "C" int m3d_head_outputs(const float* raw, int64_t N, int64_t ldr, int32_t num_classes,
                                 float* logits, float* probs, float* bbox, m3d_stream_t s) {

@@ -150,6 +150,17 @@ _SIGS = {
                            c_i32, c_i32, c_p, c_p, c_p, c_p, c_i32, c_i32, c_p, c_p, c_i64, c_p,
                            c_i64, c_i64, c_p],
     "m3d_deconv3d_k2s2": [c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i32, c_p, c_p],
+    "m3d_conv3d_bwd_data_dil": [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32,
+                                c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                c_i32, c_i32, c_i32, c_p, c_i32, c_p],
+    "m3d_conv3d_bwd_weight_dil": [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32,
+                                  c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                  c_i32, c_i32, c_i32, c_p, c_p, c_p],
+    "m3d_deconv3d_k2s2_bwd_data": [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p],
+    "m3d_deconv3d_k2s2_bwd_weight": [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p],
+    "m3d_add_f32": [c_p, c_p, c_p, c_i64, c_p],
+    "m3d_mask_out_bwd_workspace_bytes": [c_i64, c_i64, c_i32],
+    "m3d_mask_out_bwd": [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i32, c_p, c_p, c_p, c_p, c_p, c_sz, c_p],
     "m3d_head_outputs": [c_p, c_i64, c_i64, c_i32, c_p, c_p, c_p, c_p],
     "m3d_head_outputs_bwd": [c_p, c_p, c_p, c_i64, c_i64, c_i32, c_p, c_p],
     "m3d_max_norm": [c_p, c_i64, c_i64, c_f, c_p],
@@ -219,7 +230,8 @@ _RESTYPES = {"m3d_last_error": ctypes.c_char_p, "m3d_nms3d_workspace_bytes": c_s
              "m3d_conv3d_wino_u_bytes": c_sz, "m3d_conv3d_wino_tile_z": c_i32, "m3d_conv3d_wino_wgrad_tile_z": c_i32,
              "m3d_conv3d_wino_tile_y": c_i32, "m3d_conv3d_wino_dgrad_tile_y": c_i32,
              "m3d_conv3d_wino_dgrad_tile_z": c_i32, "m3d_col_sums_batched_workspace_bytes": c_sz,
-             "m3d_bn_train_few_rows_max": c_i64, "m3d_bn_train_workspace_bytes": c_sz}
+             "m3d_bn_train_few_rows_max": c_i64, "m3d_bn_train_workspace_bytes": c_sz,
+             "m3d_mask_out_bwd_workspace_bytes": c_sz}
 
 EXPORTED = tuple(_SIGS)
 
@@ -252,6 +264,7 @@ def load(path: str = LIB_PATH):
 # choice, kept here; libm3d itself holds none.
 DET_ENTRY_POINTS = ("m3d_conv3d_bwd_weight", "m3d_conv3d_bwd_weight_halo", "m3d_conv3d_bwd_weight_wino",
                     "m3d_conv3d_bwd_weight_wino_u", "m3d_conv3d_bwd_weight_wino_halo", "m3d_gemm_wgrad_f32",
+                    "m3d_conv3d_bwd_weight_dil", "m3d_deconv3d_k2s2_bwd_weight",
                     "m3d_sgd_keras", "m3d_adam_keras", "m3d_adadelta_keras")
 
 

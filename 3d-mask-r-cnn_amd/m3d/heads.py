@@ -27,9 +27,23 @@ ClassifierHead(pooled, training=True) runs its two BNs on batch statistics
 (m3d_bn_train_fwd, Keras training-mode semantics, moving statistics updated)
 and its backward (_ClassifierHeadTrain) writes the head's twelve parameter
 gradients into the ParamStore and returns the gradient of the pooled features;
-MaskRCNN.train_classifier_head is one head-only optimizer step.  The mask
-head's backward, and the join of d_pooled into PyramidROIAlign's backward and
-the trunk, are not built.
+MaskRCNN.train_classifier_head is one head-only optimizer step.  The mask head
+trains the same way (build_fpn_mask_graph(train_bn=True), core/models.py:
+1190-1238): MaskHead(pooled, training=True) runs its five BNs on batch
+statistics over all B*N*p^3 rows (momentum 0.99) and composes the backward from
+  * the conv units' own autograd (conv + bias with the tree's direct / Winograd
+    forward, data-gradient and weight-gradient routing) and _BNTrainAct;
+  * _MaskResDil: the dilated conv3b branch, whose data gradient accumulates
+    into the incoming gradient (d_res = d_x + dgrad_dil(dz), accumulate = 1);
+  * _MaskTail: m3d_mask_out_bwd (sigmoid conv backward + the deconv's ReLU mask
+    + three of the parameter gradients in one pass) and the transposed conv's
+    two gradients;
+24 parameter gradients added into the ParamStore, d_pooled returned; the weight
+gradients run on m3d.nn's weight-gradient stream and the backward pass ends
+with its join.  MaskRCNN.train_heads is one optimizer step on both heads (or
+either) against the LOSS_WEIGHTS-weighted head losses, the trunk frozen.  The
+join of d_pooled / d_mask_pooled into PyramidROIAlign's backward and the trunk
+is not built.
 """
 from __future__ import annotations
 
@@ -68,6 +82,16 @@ class DenseLayer:
         self.bias = store.add(f"{name}/bias:0", (cout,), bias_init, True)
 
 
+def _params_chunk_range(store, ps, what):
+    """(first, end) chunk of the consecutively registered parameters ``ps``."""
+    from .params import CHUNK
+    i0 = store.params.index(ps[0])
+    if store.params[i0:i0 + len(ps)] != ps:
+        raise RuntimeError(f"{what} parameters are not consecutive in the store")
+    last = ps[-1]
+    return ps[0].offset // CHUNK, (last.offset + -(-last.numel // CHUNK) * CHUNK) // CHUNK
+
+
 class ClassifierHead:
     """fpn_classifier_graph(y, pool_size, num_classes, fc_layers_size, train_bn=False)."""
 
@@ -101,13 +125,7 @@ class ClassifierHead:
         """(first, end) chunk of the head's parameters in the finalized store:
         they are registered consecutively, so KerasOptimizer.step(store,
         chunks=...) on this range is a head-only step."""
-        from .params import CHUNK
-        ps = self.params()
-        i0 = self.store.params.index(ps[0])
-        if self.store.params[i0:i0 + len(ps)] != ps:
-            raise RuntimeError("classifier head parameters are not consecutive in the store")
-        last = ps[-1]
-        return ps[0].offset // CHUNK, (last.offset + -(-last.numel // CHUNK) * CHUNK) // CHUNK
+        return _params_chunk_range(self.store, self.params(), "classifier head")
 
     def _conv1(self, x2d, bn=True):
         """[M, K] @ [K, fc] with split-K (K = pool^3 * C is ~88k for 7^3x256).
@@ -289,6 +307,10 @@ class _ClassifierHeadTrain(torch.autograd.Function):
         x, z1, y1, mean1, rstd1, z2, y2, mean2, rstd2, raw, wcat = ctx.saved_tensors
         M, nraw = raw.shape
         fc, C, dev = head.fc, head.C, raw.device
+        # the weight-gradient GEMMs below run on this stream and, in deterministic mode, through the
+        # scratch the side stream's weight gradients use (the mask head's, in a joint backward): wait
+        # for those first (nothing to wait for when the classifier trains alone)
+        mnn.join_wgrad(dev)
         g_logits = torch.zeros((M, C), device=dev) if g_logits is None else g_logits.contiguous().float()
         g_bbox = torch.zeros((M, C, 6), device=dev) if g_bbox is None else g_bbox.contiguous().float()
         g_raw = torch.empty_like(raw)
@@ -321,12 +343,169 @@ class _ClassifierHeadTrain(torch.autograd.Function):
         return d_pooled, None, None
 
 
+def _on_wgrad_stream(dev, tensors, launch):
+    """Run ``launch`` (weight-gradient launches) where the conv units run theirs:
+    on m3d.nn's side stream after a fork from the compute stream (one stream at
+    a time owns the deterministic-mode scratch), in line when that is off."""
+    from . import nn as mnn
+    side = mnn._wgrad_stream(dev)
+    if side is None:
+        launch()
+        return
+    for t in tensors:
+        t.record_stream(side)
+    with torch.cuda.stream(side):
+        launch()
+
+
+def _join_after_backward(dev):
+    """Queue m3d.nn.join_wgrad for the end of the running backward pass: the
+    compute stream then waits for the side stream's weight gradients before
+    anything enqueued after backward() reads them."""
+    from . import nn as mnn
+    torch.autograd.Variable._execution_engine.queue_callback(lambda: mnn.join_wgrad(dev))
+
+
+class _BNTrainAct(torch.autograd.Function):
+    """y = relu(BN(z)) on batch statistics over all rows of z [..., C]
+    (BatchNorm()(x, training=True) + Activation('relu'), core/models.py:1202-1203;
+    m3d_bn_train_fwd / _bwd, the moving statistics updated once per forward).
+    The backward adds dgamma / dbeta into bn's ParamStore views and returns dz.
+    ``gamma`` is bn's ParamStore view: it keeps the output in the autograd graph."""
+
+    @staticmethod
+    def forward(ctx, z, gamma, bn):
+        C = z.shape[-1]
+        z = z.contiguous()
+        z2 = z.view(-1, C)
+        y = torch.empty_like(z)
+        _, mean, rstd = bn_train_fwd(z2, bn, True, y=y.view(-1, C))
+        ctx.bn = bn
+        ctx.save_for_backward(z, y, mean, rstd)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        z, y, mean, rstd = ctx.saved_tensors
+        C = z.shape[-1]
+        dy = dy.contiguous()
+        dz = bn_train_bwd(dy.view(-1, C), y.view(-1, C), z.view(-1, C), ctx.bn, mean, rstd, True)
+        return dz.view(z.shape), None, None
+
+
+class _MaskResDil(torch.autograd.Function):
+    """x = res + relu(BN_batch(conv3b_dilated(res) + b)): mrcnn_mask_conv3b /
+    bn3b / res3 in training mode (core/models.py:1215-1222).  Returns (x, the
+    post-ReLU branch).  backward: m3d_bn_train_bwd, the dilated weight gradient
+    (m3d_conv3d_bwd_weight_dil, weight-gradient stream), the bias column sums,
+    and d_res = d_x + dgrad_dil(dz) by m3d_conv3d_bwd_data_dil with
+    accumulate = 1 into the incoming gradient's own buffer when that buffer is
+    a whole tensor (it is conv4's data gradient, which nothing else reads)."""
+
+    DIL = 2
+
+    @staticmethod
+    def forward(ctx, res, w, head):
+        L = _L()
+        layer, bn = head.convs["conv3b"]
+        res = res.contiguous()
+        M, ph, pw, pd, ch = res.shape
+        d = _MaskResDil.DIL
+        z = torch.empty_like(res)
+        check(L.m3d_conv3d_fwd_dil(ptr(res), M, ph, pw, pd, ch, ptr(layer.kernel.data), 3, 3, 3, ch, ph, pw, pd,
+                                   1, 1, 1, d, d, d, d, d, d, ptr(layer.bias.data), None, None, None, 0, 0, None,
+                                   ptr(z), ch, None, 0, 0, stream()), "mask_conv3b")
+        y = torch.empty_like(z)
+        _, mean, rstd = bn_train_fwd(z.view(-1, ch), bn, True, y=y.view(-1, ch))
+        x = torch.empty_like(res)
+        check(L.m3d_add_f32(ptr(res), ptr(y), ptr(x), res.numel(), stream()), "mask_res3")
+        ctx.head = head
+        ctx.save_for_backward(res, z, y, mean, rstd)
+        ctx.mark_non_differentiable(y)
+        return x, y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dx, _dy):
+        from . import nn as mnn
+        L = _L()
+        res, z, y, mean, rstd = ctx.saved_tensors
+        layer, bn = ctx.head.convs["conv3b"]
+        M, ph, pw, pd, ch = res.shape
+        d = _MaskResDil.DIL
+        rows = M * ph * pw * pd
+        whole = dx.is_contiguous() and dx._base is None and dx.storage_offset() == 0
+        dx = dx.contiguous()
+        dz = bn_train_bwd(dx.view(rows, ch), y.view(rows, ch), z.view(rows, ch), bn, mean, rstd, True)
+        mnn.bias_grad(dz, rows, ch, layer.bias.grad)
+        d_res = None
+        if ctx.needs_input_grad[0]:
+            d_res = dx if whole else dx.clone()
+            check(L.m3d_conv3d_bwd_data_dil(ptr(dz), ptr(layer.kernel.data), M, ph, pw, pd, ch, 3, 3, 3, ch, ph, pw,
+                                            pd, 1, 1, 1, d, d, d, d, d, d, ptr(d_res), 1, stream()),
+                  "mask_conv3b dgrad")
+        _on_wgrad_stream(res.device, (res, dz), lambda: check(
+            L.m3d_conv3d_bwd_weight_dil(ptr(res), ptr(dz), M, ph, pw, pd, ch, 3, 3, 3, ch, ph, pw, pd, 1, 1, 1,
+                                        d, d, d, d, d, d, ptr(layer.kernel.grad), stream()), "mask_conv3b wgrad"))
+        return d_res, None, None
+
+
+class _MaskTail(torch.autograd.Function):
+    """mrcnn_mask_deconv (2^3 stride-2 transposed conv + ReLU) and mrcnn_mask
+    (1^3 conv + sigmoid), core/models.py:1229-1237.  Returns (mrcnn_mask
+    [M,2p,2p,2p,C], the deconv's post-ReLU output).  backward, from the gradient
+    of the sigmoid output: m3d_mask_out_bwd (one pass: the sigmoid and ReLU
+    masks, g_up, and the mrcnn_mask kernel / bias and deconv bias gradients
+    added into their ParamStore views), then m3d_deconv3d_k2s2_bwd_weight
+    (weight-gradient stream) and m3d_deconv3d_k2s2_bwd_data."""
+
+    @staticmethod
+    def forward(ctx, x, w, head):
+        x = x.contiguous()
+        up, out = head._tail(x)
+        ctx.head = head
+        ctx.save_for_backward(x, up, out)
+        ctx.mark_non_differentiable(up)
+        return out, up
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out, _g_up):
+        L = _L()
+        head = ctx.head
+        x, up, out = ctx.saved_tensors
+        M, ph, pw, pd, ch = x.shape
+        C = head.C
+        V = up.numel() // ch
+        _join_after_backward(x.device)
+        g_out = g_out.contiguous().float()
+        g_up = torch.empty_like(up)
+        wsb = int(L.m3d_mask_out_bwd_workspace_bytes(V, ch, C))
+        ws = torch.empty(max(wsb // 4, 1), device=x.device, dtype=torch.float32)
+        check(L.m3d_mask_out_bwd(ptr(g_out), ptr(out), ptr(up), ptr(head.mask.kernel.data), V, ch, C, ptr(g_up),
+                                 ptr(head.mask.kernel.grad), ptr(head.mask.bias.grad), ptr(head.deconv_b.grad),
+                                 ptr(ws), wsb, stream()), "mask_out_bwd")
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            check(L.m3d_deconv3d_k2s2_bwd_data(ptr(g_up), ptr(head.deconv.data), M, ph, pw, pd, ch, ch, ptr(dx),
+                                               stream()), "mask_deconv dgrad")
+        _on_wgrad_stream(x.device, (x, g_up), lambda: check(
+            L.m3d_deconv3d_k2s2_bwd_weight(ptr(x), ptr(g_up), M, ph, pw, pd, ch, ch, ptr(head.deconv.grad),
+                                           stream()), "mask_deconv wgrad"))
+        return dx, None, None
+
+
 class MaskHead:
-    """build_fpn_mask_graph(y, num_classes, conv_channel, train_bn=False)."""
+    """build_fpn_mask_graph(y, num_classes, conv_channel, train_bn)."""
+
+    ACTIVATIONS = ("bn1", "bn2", "bn3", "bn3b", "bn4", "deconv")
 
     def __init__(self, store, num_classes, conv_channel, channels=256):
         ch = conv_channel
         self.C, self.ch = num_classes, ch
+        self.store = store
         self.convs = {}
         cin = channels
         for name in ("conv1", "conv2", "conv3", "conv3b", "conv4"):
@@ -342,7 +521,83 @@ class MaskHead:
         geo = conv_geom(tuple(x.shape[1:4]), (3, 3, 3), (1, 1, 1), "same")
         return conv_bn_act(x, layer, geo, True, bn=bn, need_dx=False, **kw)
 
-    def __call__(self, pooled):
+    def params(self):
+        """The head's 24 trainable tensors, in registration order: five convs x
+        (kernel, bias, gamma, beta), the deconv kernel and bias, the mrcnn_mask
+        kernel and bias."""
+        ps = []
+        for name in ("conv1", "conv2", "conv3", "conv3b", "conv4"):
+            layer, bn = self.convs[name]
+            ps += [layer.kernel, layer.bias, bn.gamma, bn.beta]
+        return ps + [self.deconv, self.deconv_b, self.mask.kernel, self.mask.bias]
+
+    def chunk_range(self):
+        """(first, end) chunk of the head's parameters in the finalized store
+        (as ClassifierHead.chunk_range)."""
+        return _params_chunk_range(self.store, self.params(), "mask head")
+
+    def _tail(self, x):
+        """(up, out): relu(deconv(x) + b) [M,2p,2p,2p,ch] and the sigmoid 1^3 conv
+        of it [M,2p,2p,2p,C], for x [M,p,p,p,ch]."""
+        L = _L()
+        M, ph, pw, pd, _ = x.shape
+        up = torch.empty((M, 2 * ph, 2 * pw, 2 * pd, self.ch), device=x.device, dtype=torch.float32)
+        check(L.m3d_deconv3d_k2s2(ptr(x), M, ph, pw, pd, self.ch, ptr(self.deconv.data), self.ch,
+                                  ptr(self.deconv_b.data), 1, ptr(up), stream()), "mask_deconv")
+        C = self.C
+        cp = -(-C // 4) * 4
+        w = torch.zeros((self.ch, cp), device=x.device, dtype=torch.float32)
+        w[:, :C] = self.mask.kernel.data.reshape(self.ch, C)
+        b = torch.zeros((cp,), device=x.device, dtype=torch.float32)
+        b[:C] = self.mask.bias.data
+        out = torch.empty((M, 2 * ph, 2 * pw, 2 * pd, C), device=x.device, dtype=torch.float32)
+        V = M * 8 * ph * pw * pd
+        spill = torch.empty((V, max(cp - C, 1)), device=x.device, dtype=torch.float32)
+        check(L.m3d_conv3d_fwd(ptr(up), 1, 1, 1, V, self.ch, ptr(w), 1, 1, 1, cp, 1, 1, V, 1, 1, 1, 0, 0, 0,
+                               ptr(b), None, None, None, 0, 2, None, ptr(out), C, ptr(spill), cp - C,
+                               C if cp > C else 0, stream()), "mrcnn_mask")
+        return up, out
+
+    def _train(self, pooled, return_activations):
+        B, N, ph, pw, pd, Cin = pooled.shape
+        x = pooled.reshape(B * N, ph, pw, pd, Cin)
+        geo = conv_geom((ph, pw, pd), (3, 3, 3), (1, 1, 1), "same")
+        acts = {}
+
+        def unit(x, name):
+            layer, bn = self.convs[name]
+            z = conv_bn_act(x, layer, geo, False, bn=None, need_dx=True)      # conv + bias
+            y = _BNTrainAct.apply(z, bn.gamma.data, bn)
+            acts["bn" + name[4:]] = y.detach()
+            return y
+        with torch.enable_grad():
+            x = unit(x, "conv1")
+            x = unit(x, "conv2")
+            res = unit(x, "conv3")
+            x, y3b = _MaskResDil.apply(res, self.convs["conv3b"][0].kernel.data, self)
+            acts["bn3b"] = y3b
+            x = unit(x, "conv4")
+            out, up = _MaskTail.apply(x, self.deconv.data, self)
+        acts["deconv"] = up
+        out = out.view(B, N, 2 * ph, 2 * pw, 2 * pd, self.C)
+        if return_activations:
+            return out, {k: acts[k] for k in self.ACTIVATIONS}
+        return out
+
+    def __call__(self, pooled, training=False, return_activations=False):
+        """training=False: moving-statistics BN (the inference graph).
+        training=True: every BN on batch statistics over all B*N*p^3 rows
+        (zero-padded ROIs included, as under TimeDistributed), the moving
+        statistics updated once with momentum 0.99 (BatchNorm()'s default);
+        the output carries the head's backward, which ADDS the 24 parameter
+        gradients into their ParamStore views and yields d_pooled when pooled
+        requires grad.  return_activations (training mode): also a dict of the
+        six post-ReLU tensors bn1, bn2, bn3, bn3b, bn4 [B*N,p,p,p,ch] and deconv
+        [B*N,2p,2p,2p,ch]."""
+        if training:
+            return self._train(pooled, return_activations)
+        if return_activations:
+            raise ValueError("MaskHead: return_activations needs training=True")
         B, N, ph, pw, pd, Cin = pooled.shape
         L = _L()
         x = pooled.reshape(B * N, ph, pw, pd, Cin).contiguous()
@@ -359,22 +614,8 @@ class MaskHead:
                                    ptr(shift), ptr(res), 3, 1, None, ptr(x), self.ch, None, 0, 0, stream()),
               "mask_conv3b")
         x = self._same(x, "conv4")
-        up = torch.empty((M, 2 * ph, 2 * pw, 2 * pd, self.ch), device=x.device, dtype=torch.float32)
-        check(L.m3d_deconv3d_k2s2(ptr(x), M, ph, pw, pd, self.ch, ptr(self.deconv.data), self.ch,
-                                  ptr(self.deconv_b.data), 1, ptr(up), stream()), "mask_deconv")
-        C = self.C
-        cp = -(-C // 4) * 4
-        w = torch.zeros((self.ch, cp), device=x.device, dtype=torch.float32)
-        w[:, :C] = self.mask.kernel.data.reshape(self.ch, C)
-        b = torch.zeros((cp,), device=x.device, dtype=torch.float32)
-        b[:C] = self.mask.bias.data
-        out = torch.empty((B, N, 2 * ph, 2 * pw, 2 * pd, C), device=x.device, dtype=torch.float32)
-        spill = torch.empty((M * 8 * ph * pw * pd, max(cp - C, 1)), device=x.device, dtype=torch.float32)
-        V = M * 8 * ph * pw * pd
-        check(L.m3d_conv3d_fwd(ptr(up), 1, 1, 1, V, self.ch, ptr(w), 1, 1, 1, cp, 1, 1, V, 1, 1, 1, 0, 0, 0,
-                               ptr(b), None, None, None, 0, 2, None, ptr(out), C, ptr(spill), cp - C,
-                               C if cp > C else 0, stream()), "mrcnn_mask")
-        return out
+        _, out = self._tail(x)
+        return out.view(B, N, 2 * ph, 2 * pw, 2 * pd, self.C)
 
 
 class DetectionLayer:
@@ -567,6 +808,86 @@ class MaskRCNN:
         apply_max_norm(self.store, self.classifier.max_norm_constraints)
         return {"loss": total.detach(), "mrcnn_class_loss": lc, "mrcnn_bbox_loss": lb, "d_pooled": pooled.grad,
                 "rois": rois, "target_class_ids": target_class_ids, "target_bbox": target_bbox}
+
+    def train_heads(self, image, image_meta, gt_class_ids, gt_boxes, gt_masks, optimizer, seed=None,
+                    heads=("classifier", "mask")):
+        """One optimizer step on the selected heads with the trunk frozen (the
+        head part of TRAIN_PHASE="heads", core/models.py:5602-5668):
+
+          1. trunk, proposals, DetectionTargetLayer and PyramidROIAlign(POOL_SIZE) /
+             (MASK_POOL_SIZE) under no_grad, as in head_losses;
+          2. the selected heads in training mode (batch-statistics BN, moving
+             statistics updated);
+          3. the LOSS_WEIGHTS-weighted sum of the selected heads' losses
+             (mrcnn_class_loss + mrcnn_bbox_loss for "classifier",
+             mrcnn_mask_loss for "mask");
+          4. backward into the ParamStore gradients of those heads;
+          5. ``optimizer`` (a KerasOptimizer) on the selected heads' chunk ranges
+             (one launch over both when they are adjacent in the store);
+          6. MaxNorm on the two Dense kernels when the classifier is selected.
+
+        Returns a dict: "loss" and the selected heads' losses (device scalars,
+        evaluated before the update), the sampled "rois", "target_class_ids",
+        "target_bbox", "target_mask", and "d_pooled" / "d_mask_pooled", the loss
+        gradient with respect to the pooled features of each selected head.
+        With heads=("classifier",) it is train_classifier_head.  The join of the
+        two pooled gradients through PyramidROIAlign's backward into the trunk is
+        not built."""
+        from . import nn as mnn
+        from .head_losses import LOSS_NAMES, active_class_ids_from_meta, mrcnn_losses
+        from .optim import apply_max_norm
+        from .params import CHUNK
+        heads = tuple(heads)
+        if not heads or len(set(heads)) != len(heads) or any(h not in ("classifier", "mask") for h in heads):
+            raise ValueError('train_heads: heads must be a non-empty subset of ("classifier", "mask")')
+        cls, msk = "classifier" in heads, "mask" in heads
+        c = self.config
+        ops._dev(image, image_meta, gt_class_ids, gt_boxes, gt_masks)
+        pooled = mpooled = None
+        with torch.no_grad():
+            _, rois, _, target_class_ids, target_bbox, target_mask, mrcnn_maps = \
+                self._head_targets(image, image_meta, gt_class_ids, gt_boxes, gt_masks, seed)
+            if cls:
+                pooled = self.roi_align_classifier([rois, image_meta] + mrcnn_maps)
+            if msk:
+                mpooled = self.roi_align_mask([rois, image_meta] + mrcnn_maps)
+        ranges = []
+        if cls:
+            pooled = pooled.detach().requires_grad_(True)
+            ranges.append(self.classifier.chunk_range())
+        if msk:
+            mpooled = mpooled.detach().requires_grad_(True)
+            ranges.append(self.mask_head.chunk_range())
+        ranges.sort()
+        if len(ranges) == 2:
+            # one optimizer step (one step count) covers both: the heads are registered back to back
+            if ranges[0][1] != ranges[1][0]:
+                raise RuntimeError("train_heads: the two heads' parameters are not adjacent in the store")
+            ranges = [(ranges[0][0], ranges[1][1])]
+        for lo, hi in ranges:
+            self.store.grad_flat[lo * CHUNK:hi * CHUNK].zero_()
+        logits = bbox = mask = None
+        if cls:
+            logits, _, bbox = self.classifier(pooled, training=True)
+        if msk:
+            mask = self.mask_head(mpooled, training=True)
+        lw = getattr(c, "LOSS_WEIGHTS", {})
+        weights = tuple(float(lw.get(n, 1.0)) for n in LOSS_NAMES)
+        total, lc, lb, lm = mrcnn_losses(target_class_ids, target_bbox if cls else None,
+                                         target_mask if msk else None, logits, bbox, mask,
+                                         active_class_ids_from_meta(image_meta), weights)
+        total.backward()
+        mnn.join_wgrad(self.device)
+        optimizer.step(self.store, chunks=ranges[0])
+        if cls:
+            apply_max_norm(self.store, self.classifier.max_norm_constraints)
+        r = {"loss": total.detach(), "rois": rois, "target_class_ids": target_class_ids, "target_bbox": target_bbox,
+             "target_mask": target_mask}
+        if cls:
+            r.update(mrcnn_class_loss=lc, mrcnn_bbox_loss=lb, d_pooled=pooled.grad)
+        if msk:
+            r.update(mrcnn_mask_loss=lm, d_mask_pooled=mpooled.grad)
+        return r
 
     def load_weights(self, filepath, by_name=True, skip_mismatch=False, exclude=()):
         """keras_model.load_weights(filepath, by_name=True, ...) on the Keras-H5 format (m3d.weights)."""

@@ -586,6 +586,65 @@ int m3d_deconv3d_k2s2(const float* x, int64_t B, int64_t H, int64_t W, int64_t D
                       m3d_stream_t s);
 
 /* ---------------------------------------------------------------------------
+ * Backward of the mask head (build_fpn_mask_graph(train_bn=True),
+ * core/models.py:1190-1238).
+ * ------------------------------------------------------------------------- */
+/* m3d_conv3d_bwd_data for a dilated conv (mrcnn_mask_conv3b, dilation (2,2,2),
+ * core/models.py:1215-1218): dx (+)= the same conv over dz on the flipped taps,
+ * stepped by (dly,dlx,dlz), with pad' = dl*(k-1) - pad.  Stride 1 only, any
+ * kernel, accumulate 0 (overwrite) or 1 (add to dx: the residual join
+ * mrcnn_mask_res3, core/models.py:1222).  Cout % 32 == 0, Cin % 4 == 0.  At
+ * dilation 1 it is m3d_conv3d_bwd_data, bit for bit. */
+int m3d_conv3d_bwd_data_dil(const float* dz, const float* w, int64_t B, int64_t H, int64_t W,
+                            int64_t D, int64_t Cin, int32_t kh, int32_t kw, int32_t kd, int64_t Cout,
+                            int64_t OH, int64_t OW, int64_t OD, int32_t sy, int32_t sx, int32_t sz,
+                            int32_t py, int32_t px, int32_t pz, int32_t dly, int32_t dlx, int32_t dlz,
+                            float* dx, int32_t accumulate, m3d_stream_t s);
+/* out = a + b over n floats (n % 4 == 0; out aliases neither input): KL.Add of the two
+ * activated branches of mrcnn_mask_res3 (core/models.py:1222) in training mode,
+ * where the second branch leaves a batch-statistics BN, not a conv epilogue. */
+int m3d_add_f32(const float* a, const float* b, float* out, int64_t n, m3d_stream_t s);
+/* m3d_conv3d_bwd_weight with the dilation (dly,dlx,dlz) on the im2col taps
+ * (mrcnn_mask_conv3b, core/models.py:1215-1218); the same det argument and
+ * determinism rules.  m3d_conv3d_bwd_weight is this call at dilation 1. */
+int m3d_conv3d_bwd_weight_dil(const float* x, const float* dz, int64_t B, int64_t H, int64_t W,
+                              int64_t D, int64_t Cin, int32_t kh, int32_t kw, int32_t kd,
+                              int64_t Cout, int64_t OH, int64_t OW, int64_t OD, int32_t sy,
+                              int32_t sx, int32_t sz, int32_t py, int32_t px, int32_t pz,
+                              int32_t dly, int32_t dlx, int32_t dlz, float* dw,
+                              const m3d_det_t* det, m3d_stream_t s);
+/* Backward of m3d_deconv3d_k2s2 (mrcnn_mask_deconv, core/models.py:1230-1233)
+ * from g [B,2H,2W,2D,Cout], the gradient of the transposed conv's output
+ * BEFORE its activation (m3d_mask_out_bwd applies the ReLU mask):
+ *   bwd_data:   dx [B,H,W,D,Cin] = sum_{t,o} g[2i+t, o] w[t,o,c]  (written whole);
+ *   bwd_weight: dw [2,2,2,Cout,Cin] += sum_i g[2i+t, o] x[i, c]   (det as
+ *               m3d_conv3d_bwd_weight; zero dw before the first accumulation).
+ * The Keras kernel is read in place as the conv kernel [2,2,2,Cin'=Cout,Cout'=Cin]
+ * of a 2^3 stride-2 'valid' conv.  Cin % 4 == 0, Cout % 4 == 0. */
+int m3d_deconv3d_k2s2_bwd_data(const float* g, const float* w, int64_t B, int64_t H, int64_t W, int64_t D,
+                               int64_t Cin, int64_t Cout, float* dx, m3d_stream_t s);
+int m3d_deconv3d_k2s2_bwd_weight(const float* x, const float* g, int64_t B, int64_t H, int64_t W, int64_t D,
+                                 int64_t Cin, int64_t Cout, float* dw, const m3d_det_t* det, m3d_stream_t s);
+/* Backward of mrcnn_mask (Conv3D(C, 1^3), sigmoid, core/models.py:1234-1237)
+ * joined with the ReLU of mrcnn_mask_deconv (core/models.py:1230-1233), one
+ * pass over V = rois * (2p)^3 rows: g_mask [V,C] the gradient of the sigmoid
+ * output, out [V,C] that output, up [V,ch] the deconv's post-ReLU output,
+ * w [ch,C] the mrcnn_mask kernel.  With gl = g_mask out (1 - out):
+ *   g_up[v,c]        = (sum_k gl[v,k] w[c,k]) (up[v,c] > 0)     written whole
+ *   dW[c,k]         += sum_v up[v,c] gl[v,k]
+ *   db[k]           += sum_v gl[v,k]
+ *   d_deconv_bias[c] += sum_v g_up[v,c]
+ * The three sums go through per-workgroup partials in the workspace
+ * (m3d_mask_out_bwd_workspace_bytes; its contents need no initialisation)
+ * folded in a fixed order: no atomics, two runs are bit-identical.
+ * 1 <= C <= 8, ch % 4 == 0, ch <= 1024; g_up must not alias up.  64-bit
+ * addressing throughout: no 4 GiB operand bound. */
+size_t m3d_mask_out_bwd_workspace_bytes(int64_t V, int64_t ch, int32_t C);
+int m3d_mask_out_bwd(const float* g_mask, const float* out, const float* up, const float* w, int64_t V,
+                     int64_t ch, int32_t C, float* g_up, float* dW, float* db, float* d_deconv_bias,
+                     void* workspace, size_t ws_bytes, m3d_stream_t s);
+
+/* ---------------------------------------------------------------------------
  * Mask R-CNN head glue (core/models.py:1121-1190, 1415-1575).
  * m3d_head_outputs: raw [N][ldr] = [class logits (C) | bbox deltas (6C)] of
  *   the two TimeDistributed Dense layers -> logits [N,C] clipped to [-10,10],
