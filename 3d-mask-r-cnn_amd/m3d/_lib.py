@@ -183,6 +183,11 @@ _SIGS = {
                           c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p],
     "m3d_head_loss_bwd": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_f, c_f, c_p, c_p, c_p,
                           c_p, c_p, c_p],
+    "m3d_unmold_prepare": [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p],
+    "m3d_unmold_overlaps": [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_p],
+    "m3d_unmold_finalize": [c_p, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p],
+    "m3d_unmold_paste": [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p],
+    "m3d_mask_areas": [c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p],
     "m3d_maxpool3d_fwd": [c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32,
                           c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, c_p, c_p, c_p],
     "m3d_maxpool3d_bwd": [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32,

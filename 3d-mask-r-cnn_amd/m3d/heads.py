@@ -914,3 +914,23 @@ class MaskRCNN:
         return {"detections": detections, "mrcnn_class": mrcnn_class, "mrcnn_bbox": mrcnn_bbox,
                 "mrcnn_mask": mrcnn_mask, "rpn_rois": rpn_rois, "feature_maps": fmaps,
                 "pooled": pooled, "mask_pooled": mpooled, "rpn_class": rpn_probs, "rpn_bbox": rpn_bbox}
+
+    @torch.no_grad()
+    def evaluate(self, image, image_meta, gt_class_ids, gt_boxes, gt_masks, iou_threshold=0.5):
+        """The reference's MRCNN_EVALUATION for one image [1,H,W,D,Cin]: detect ->
+        unmold_detections -> mask overlaps against gt_masks [H,W,D,G] (or
+        [1,H,W,D,G]; uint8, G innermost) -> compute_ap (m3d.evaluate).  Returns
+        evaluate_detections' dict (mAP, precision, recall, ious, iou, ...) plus
+        ``detections`` and ``mrcnn_mask``.  gt_boxes is accepted for the
+        reference's signature; the mask IoU does not read it."""
+        from .evaluate import evaluate_detections
+        ops._dev(image, image_meta, gt_masks)
+        if image.shape[0] != 1:
+            raise ValueError("MaskRCNN.evaluate takes one image; loop over a batch")
+        r = self.detect(image, image_meta)
+        if torch.is_tensor(gt_class_ids) and gt_class_ids.dim() == 2:
+            gt_class_ids = gt_class_ids[0]
+        out = evaluate_detections(r["detections"][0], r["mrcnn_mask"][0], tuple(image.shape[1:4]), gt_class_ids,
+                                  gt_masks, iou_threshold)
+        out["detections"], out["mrcnn_mask"] = r["detections"], r["mrcnn_mask"]
+        return out

@@ -793,6 +793,54 @@ int m3d_head_loss_bwd(const float* class_logits, const float* bbox_pred, const f
                       float alpha, float gamma, const float* state, const float* g_total, float* g_logits,
                       float* g_bbox, float* g_mask, m3d_stream_t s);
 
+/* Detection unmolding and mask-IoU evaluation (MRCNN_EVALUATION): the masks of
+ * unmold_detections / unmold_small_3d_mask (core/models.py:7198-7419) and the
+ * counts of compute_overlaps_masks (core/utils.py:312-334) for one image,
+ * without building the reference's [H,W,D,N] masks.  detections [max_inst,8]
+ * (normalised box, class id, score), mrcnn_mask [max_inst,m,m,m,C]
+ * probabilities, gt_masks [H,W,D,G] uint8 (G innermost, set = non-zero; the
+ * layout m3d_mask_targets3d reads).  Scalar arithmetic is fp64 on the fp32
+ * inputs in the order of tests/unmoldref.py; the counts are integers, so every
+ * output is run-to-run bit-identical.
+ *   m3d_unmold_prepare   box_i [max_inst,6] int32 (y1,x1,z1,y2,x2,z2 clipped to
+ *     the volume), status [max_inst] int32 (M3D_UNMOLD_*), stats [max_inst,8]
+ *     double (min, max, mean, std, p50, p95, thr, resize_thr) and small
+ *     [max_inst,m^3] uint8, the thresholded and cleaned grid (all zero unless
+ *     the status is OK).  m^3 <= 32768: the grid is sorted in LDS.
+ *   m3d_unmold_overlaps  area_pred [max_inst] int32 = set voxels of the resized
+ *     mask, inter [max_inst,G] int32 = those also set in GT mask g; both are
+ *     zeroed first.  G may be 0 (gt_masks / inter unused).
+ *   m3d_mask_areas       area_gt [G] int32 (zeroed first).
+ *   m3d_unmold_finalize  status OK -> SPARSE where area_pred / box volume <
+ *     1e-5; the rows of area_pred / inter whose status is not OK are zeroed;
+ *     iou [max_inst,G] float (may be NULL; needs area_gt) = inter / (area_pred
+ *     + area_gt - inter) in IEEE float32, 0 / 0 = NaN.
+ *   m3d_unmold_paste     writes 1 at every set voxel into dense
+ *     [max_inst,H,W,D] uint8 and / or seg_union [H,W,D] uint8 (either may be
+ *     NULL; the caller zero-fills them); run it after m3d_unmold_finalize.
+ * M3D_EINVAL before any launch: NULL pointers, m^3 > 32768, non-positive m / H
+ * / W / D / C, H W D beyond 31 bits, negative max_inst or G. */
+#define M3D_UNMOLD_OK 0
+#define M3D_UNMOLD_NOT_KEPT 1   /* class id 0 or a box extent <= 0.5 voxel */
+#define M3D_UNMOLD_RANGE 2      /* min < -0.1 or max > 1.1: logits, not converted here */
+#define M3D_UNMOLD_FLAT 3       /* std < 1e-6 */
+#define M3D_UNMOLD_FAINT 4      /* 95th percentile < 0.10 */
+#define M3D_UNMOLD_EMPTY 5      /* under 0.01 % of the grid passes the threshold */
+#define M3D_UNMOLD_SPARSE 6     /* under 0.001 % of the box is set after the resize */
+int m3d_unmold_prepare(const float* detections, const float* mrcnn_mask, int64_t max_inst, int64_t m, int64_t C,
+                       int64_t H, int64_t W, int64_t D, uint8_t* small, int32_t* box_i, int32_t* status,
+                       double* stats, m3d_stream_t s);
+int m3d_unmold_overlaps(const uint8_t* small, const int32_t* box_i, const int32_t* status, const double* stats,
+                        int64_t max_inst, int64_t m, int64_t H, int64_t W, int64_t D, const uint8_t* gt_masks,
+                        int64_t G, int32_t* area_pred, int32_t* inter, m3d_stream_t s);
+int m3d_unmold_finalize(const int32_t* box_i, int32_t* status, int64_t max_inst, int64_t G, int32_t* area_pred,
+                        int32_t* inter, const int32_t* area_gt, float* iou, m3d_stream_t s);
+int m3d_unmold_paste(const uint8_t* small, const int32_t* box_i, const int32_t* status, const double* stats,
+                     int64_t max_inst, int64_t m, int64_t H, int64_t W, int64_t D, uint8_t* dense,
+                     uint8_t* seg_union, m3d_stream_t s);
+int m3d_mask_areas(const uint8_t* gt_masks, int64_t H, int64_t W, int64_t D, int64_t G, int32_t* area_gt,
+                   m3d_stream_t s);
+
 /* ---------------------------------------------------------------------------
  * Elementwise / reduction kernels of the backbone-FPN-RPN graph.
  * ------------------------------------------------------------------------- */
