@@ -163,33 +163,40 @@ class ClassifierHead:
         if training:
             return _ClassifierHeadTrain.apply(pooled, self.conv1.kernel.data, self)
         B, N = pooled.shape[:2]
-        M = B * N
-        L = _L()
-        x = pooled.reshape(M, -1).contiguous()
-        h = self._conv1(x)
+        h = self._conv1(pooled.reshape(B * N, -1).contiguous())
         scale, shift = _bn_affine(self.bn2)
         h2 = torch.empty_like(h)
-        check(L.m3d_conv3d_fwd(ptr(h), 1, 1, 1, M, self.fc, ptr(self.conv2.kernel.data), 1, 1, 1, self.fc,
-                               1, 1, M, 1, 1, 1, 0, 0, 0, ptr(self.conv2.bias.data), ptr(scale),
-                               ptr(shift), None, 0, 1, None, ptr(h2), self.fc, None, 0, 0, stream()),
-              "class_conv2")
-        C = self.C
-        nraw = -(-7 * C // 4) * 4
-        wcat = torch.zeros((self.fc, nraw), device=h.device, dtype=torch.float32)
+        _conv1_rows(h, self.conv2.kernel.data, self.conv2.bias.data, h2, "class_conv2", scale, shift, act=1)
+        return self._outputs(h2, B, N, 4)[:3]
+
+    def _dense_cat(self, pad):
+        """(wcat [fc, nraw], bcat [nraw], nraw): the two Dense layers' kernels and
+        biases side by side, the 7 C columns zero-padded to a multiple of ``pad``."""
+        C, dev = self.C, self.logits.kernel.data.device
+        nraw = -(-7 * C // pad) * pad
+        wcat = torch.zeros((self.fc, nraw), device=dev, dtype=torch.float32)
         wcat[:, :C] = self.logits.kernel.data
         wcat[:, C:7 * C] = self.bbox.kernel.data
-        bcat = torch.zeros((nraw,), device=h.device, dtype=torch.float32)
+        bcat = torch.zeros((nraw,), device=dev, dtype=torch.float32)
         bcat[:C] = self.logits.bias.data
         bcat[C:7 * C] = self.bbox.bias.data
+        return wcat, bcat, nraw
+
+    def _outputs(self, h, B, N, pad):
+        """The concatenated Dense GEMM on h [B*N, fc] and m3d_head_outputs (clip,
+        softmax, bbox reshape): (logits, probs, bbox, raw, wcat)."""
+        L = _L()
+        M, C = B * N, self.C
+        wcat, bcat, nraw = self._dense_cat(pad)
         raw = torch.empty((M, nraw), device=h.device, dtype=torch.float32)
-        check(L.m3d_gemm_f32_ex(ptr(h2), self.fc, 0, ptr(wcat), 0, ptr(raw), 0, 1, M, self.fc, nraw,
+        check(L.m3d_gemm_f32_ex(ptr(h), self.fc, 0, ptr(wcat), 0, ptr(raw), 0, 1, M, self.fc, nraw,
                                 ptr(bcat), 0, 0, stream()), "class dense")
         logits = torch.empty((B, N, C), device=h.device, dtype=torch.float32)
         probs = torch.empty_like(logits)
         bbox = torch.empty((B, N, C, 6), device=h.device, dtype=torch.float32)
         check(L.m3d_head_outputs(ptr(raw), M, nraw, C, ptr(logits), ptr(probs), ptr(bbox), stream()),
               "head_outputs")
-        return logits, probs, bbox
+        return logits, probs, bbox, raw, wcat
 
 
 def bn_train_few_rows_max():
@@ -241,6 +248,18 @@ def _dgrad1(dz, w, cin):
     return dx
 
 
+def _conv1_rows(x, w, b, out, what, scale=None, shift=None, act=0, spill=None):
+    """out = act(BN(x w + b)) for x [M rows, cin] and a kernel w [..., cin, cout]:
+    the 1^3 form of m3d_conv3d_fwd over M 'voxels' (act 0 none, 1 ReLU, 2
+    sigmoid).  out holds the first out.shape[-1] columns; the padded rest, if
+    any, goes to ``spill``."""
+    cin, cout = w.shape[-2:]
+    M, n = x.numel() // cin, out.shape[-1]
+    check(_L().m3d_conv3d_fwd(ptr(x), 1, 1, 1, M, cin, ptr(w), 1, 1, 1, cout, 1, 1, M, 1, 1, 1, 0, 0, 0, ptr(b),
+                              ptr(scale), ptr(shift), None, 0, act, None, ptr(out), n, ptr(spill), cout - n,
+                              n if cout > n else 0, stream()), what)
+
+
 def _wgrad(a, b, dw):
     """dw [K, N] += a^T b for a [M, K], b [M, N] (m3d_gemm_wgrad_f32; follows
     the process's deterministic mode)."""
@@ -264,35 +283,16 @@ class _ClassifierHeadTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pooled, w, head):
-        L = _L()
         B, N = pooled.shape[:2]
-        M, fc, C = B * N, head.fc, head.C
-        x = pooled.detach().reshape(M, -1).contiguous()
-        dev = x.device
+        x = pooled.detach().reshape(B * N, -1).contiguous()
         z1 = head._conv1(x, bn=False)
         y1, mean1, rstd1 = bn_train_fwd(z1, head.bn1, True)
         z2 = torch.empty_like(z1)
-        check(L.m3d_conv3d_fwd(ptr(y1), 1, 1, 1, M, fc, ptr(head.conv2.kernel.data), 1, 1, 1, fc,
-                               1, 1, M, 1, 1, 1, 0, 0, 0, ptr(head.conv2.bias.data), None, None, None, 0, 0,
-                               None, ptr(z2), fc, None, 0, 0, stream()), "class_conv2")
+        _conv1_rows(y1, head.conv2.kernel.data, head.conv2.bias.data, z2, "class_conv2")
         y2, mean2, rstd2 = bn_train_fwd(z2, head.bn2, True)
         # raw columns padded to a multiple of 32: the data gradient g_raw Wcat^T runs
         # on m3d_conv3d_bwd_data, whose reduction (here nraw) is a multiple of 32
-        nraw = -(-7 * C // 32) * 32
-        wcat = torch.zeros((fc, nraw), device=dev, dtype=torch.float32)
-        wcat[:, :C] = head.logits.kernel.data
-        wcat[:, C:7 * C] = head.bbox.kernel.data
-        bcat = torch.zeros((nraw,), device=dev, dtype=torch.float32)
-        bcat[:C] = head.logits.bias.data
-        bcat[C:7 * C] = head.bbox.bias.data
-        raw = torch.empty((M, nraw), device=dev, dtype=torch.float32)
-        check(L.m3d_gemm_f32_ex(ptr(y2), fc, 0, ptr(wcat), 0, ptr(raw), 0, 1, M, fc, nraw, ptr(bcat), 0, 0,
-                                stream()), "class dense")
-        logits = torch.empty((B, N, C), device=dev, dtype=torch.float32)
-        probs = torch.empty_like(logits)
-        bbox = torch.empty((B, N, C, 6), device=dev, dtype=torch.float32)
-        check(L.m3d_head_outputs(ptr(raw), M, nraw, C, ptr(logits), ptr(probs), ptr(bbox), stream()),
-              "head_outputs")
+        logits, probs, bbox, raw, wcat = head._outputs(y2, B, N, 32)
         ctx.head, ctx.shape = head, tuple(pooled.shape)
         ctx.save_for_backward(x, z1, y1, mean1, rstd1, z2, y2, mean2, rstd2, raw, wcat)
         ctx.mark_non_differentiable(probs)
@@ -553,9 +553,7 @@ class MaskHead:
         out = torch.empty((M, 2 * ph, 2 * pw, 2 * pd, C), device=x.device, dtype=torch.float32)
         V = M * 8 * ph * pw * pd
         spill = torch.empty((V, max(cp - C, 1)), device=x.device, dtype=torch.float32)
-        check(L.m3d_conv3d_fwd(ptr(up), 1, 1, 1, V, self.ch, ptr(w), 1, 1, 1, cp, 1, 1, V, 1, 1, 1, 0, 0, 0,
-                               ptr(b), None, None, None, 0, 2, None, ptr(out), C, ptr(spill), cp - C,
-                               C if cp > C else 0, stream()), "mrcnn_mask")
+        _conv1_rows(up, w, b, out, "mrcnn_mask", act=2, spill=spill)
         return up, out
 
     def _train(self, pooled, return_activations):
@@ -742,16 +740,14 @@ class MaskRCNN:
         reference's training graph runs the head BNs on batch statistics
         (train_bn=True, core/models.py:5624,5636), so this is the validation
         score of a checkpoint, not that graph's training-mode value."""
-        from .head_losses import LOSS_NAMES, active_class_ids_from_meta, mrcnn_losses
-        c = self.config
+        from .head_losses import active_class_ids_from_meta, mrcnn_losses
         rpn_rois, rois, target_gt_boxes, target_class_ids, target_bbox, target_mask, mrcnn_maps = \
             self._head_targets(image, image_meta, gt_class_ids, gt_boxes, gt_masks, seed)
         pooled = self.roi_align_classifier([rois, image_meta] + mrcnn_maps)
         logits, probs, bbox = self.classifier(pooled)
         mrcnn_mask = self.mask_head(self.roi_align_mask([rois, image_meta] + mrcnn_maps))
         active = active_class_ids_from_meta(image_meta)
-        lw = getattr(c, "LOSS_WEIGHTS", {})
-        weights = tuple(float(lw.get(n, 1.0)) for n in LOSS_NAMES)
+        weights = self._loss_weights()
         total, lc, lb, lm = mrcnn_losses(target_class_ids, target_bbox, target_mask, logits, bbox, mrcnn_mask,
                                          active, weights)
         return {"loss": total, "mrcnn_class_loss": lc, "mrcnn_bbox_loss": lb, "mrcnn_mask_loss": lm,
@@ -786,28 +782,16 @@ class MaskRCNN:
         backpropagates the head losses into every trainable layer; here only the
         classifier head moves.  d_pooled is where that backward would continue:
         its join through PyramidROIAlign's backward into the trunk is not built."""
-        from .head_losses import LOSS_NAMES, active_class_ids_from_meta, mrcnn_losses
-        from .optim import apply_max_norm
-        c = self.config
-        ops._dev(image, image_meta, gt_class_ids, gt_boxes, gt_masks)
-        with torch.no_grad():
-            _, rois, _, target_class_ids, target_bbox, _, mrcnn_maps = \
-                self._head_targets(image, image_meta, gt_class_ids, gt_boxes, gt_masks, seed)
-            pooled = self.roi_align_classifier([rois, image_meta] + mrcnn_maps)
-        pooled = pooled.detach().requires_grad_(True)
-        lo, hi = self.classifier.chunk_range()
-        from .params import CHUNK
-        self.store.grad_flat[lo * CHUNK:hi * CHUNK].zero_()
-        logits, _, bbox = self.classifier(pooled, training=True)
-        lw = getattr(c, "LOSS_WEIGHTS", {})
-        weights = tuple(float(lw.get(n, 1.0)) for n in LOSS_NAMES)
-        total, lc, lb, _ = mrcnn_losses(target_class_ids, target_bbox, None, logits, bbox, None,
-                                        active_class_ids_from_meta(image_meta), weights)
-        total.backward()
-        optimizer.step(self.store, chunks=(lo, hi))
-        apply_max_norm(self.store, self.classifier.max_norm_constraints)
-        return {"loss": total.detach(), "mrcnn_class_loss": lc, "mrcnn_bbox_loss": lb, "d_pooled": pooled.grad,
-                "rois": rois, "target_class_ids": target_class_ids, "target_bbox": target_bbox}
+        r = self.train_heads(image, image_meta, gt_class_ids, gt_boxes, gt_masks, optimizer, seed=seed,
+                             heads=("classifier",))
+        return {k: r[k] for k in ("loss", "mrcnn_class_loss", "mrcnn_bbox_loss", "d_pooled", "rois",
+                                  "target_class_ids", "target_bbox")}
+
+    def _loss_weights(self):
+        """The config's LOSS_WEIGHTS of the three head losses, in LOSS_NAMES order (1 where unset)."""
+        from .head_losses import LOSS_NAMES
+        lw = getattr(self.config, "LOSS_WEIGHTS", {})
+        return tuple(float(lw.get(n, 1.0)) for n in LOSS_NAMES)
 
     def train_heads(self, image, image_meta, gt_class_ids, gt_boxes, gt_masks, optimizer, seed=None,
                     heads=("classifier", "mask")):
@@ -834,14 +818,13 @@ class MaskRCNN:
         two pooled gradients through PyramidROIAlign's backward into the trunk is
         not built."""
         from . import nn as mnn
-        from .head_losses import LOSS_NAMES, active_class_ids_from_meta, mrcnn_losses
+        from .head_losses import active_class_ids_from_meta, mrcnn_losses
         from .optim import apply_max_norm
         from .params import CHUNK
         heads = tuple(heads)
         if not heads or len(set(heads)) != len(heads) or any(h not in ("classifier", "mask") for h in heads):
             raise ValueError('train_heads: heads must be a non-empty subset of ("classifier", "mask")')
         cls, msk = "classifier" in heads, "mask" in heads
-        c = self.config
         ops._dev(image, image_meta, gt_class_ids, gt_boxes, gt_masks)
         pooled = mpooled = None
         with torch.no_grad():
@@ -871,11 +854,9 @@ class MaskRCNN:
             logits, _, bbox = self.classifier(pooled, training=True)
         if msk:
             mask = self.mask_head(mpooled, training=True)
-        lw = getattr(c, "LOSS_WEIGHTS", {})
-        weights = tuple(float(lw.get(n, 1.0)) for n in LOSS_NAMES)
         total, lc, lb, lm = mrcnn_losses(target_class_ids, target_bbox if cls else None,
                                          target_mask if msk else None, logits, bbox, mask,
-                                         active_class_ids_from_meta(image_meta), weights)
+                                         active_class_ids_from_meta(image_meta), self._loss_weights())
         total.backward()
         mnn.join_wgrad(self.device)
         optimizer.step(self.store, chunks=ranges[0])

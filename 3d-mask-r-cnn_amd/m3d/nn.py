@@ -324,13 +324,12 @@ CONV1_X3_DGRAD_TILES = 256
 CONV1_X3_MIN_K = 32             # forward; round 4: 256 (and 256 tiles)
 CONV1_X3_DGRAD_MIN_K = 256
 # the data gradient with the producer's BN-ReLU backward fused into the split
-# GEMM (m3d_conv3d_bwd_data_x3_bna): its own K floor, and whether it also takes
-# the accumulating (identity blocks' 2a) gradients.  Round 6 A/B of K >= 32 with
+# GEMM (m3d_conv3d_bwd_data_x3_bna): its own K floor; it never takes the
+# accumulating (identity blocks' 2a) gradients.  Round 6 A/B of K >= 32 with
 # accumulate against the round-5 rule (K >= 256, no accumulate), same box
 # (scripts/r06/gpu_bna.sh, profiles/r06_x3_bna_ab.txt): 128^3 24.58 vs 24.50 ms,
 # 256^3 148.4 vs 148.9 ms -- neutral, so the round-5 rule stays.
 CONV1_X3_DGRAD_FUSED_MIN_K = 256
-X3_BN_FUSE_ACC = False
 
 
 def _conv1_x3(xshape, geo, K, N, bwd_data=False, fused=False):
@@ -567,10 +566,6 @@ WINO_V_PREPASS_MIN_VOXELS = 128 ** 3
 WINO_V = WinoVPrep()
 
 
-def _x3_planes(w, cin, cout, transpose):
-    return X3_PLANES.get(w, cin, cout, transpose)
-
-
 def _shared_wino_ws(wshare, role, ws, wsb, tag=None):
     """Workspace of a Winograd conv whose kernel is shared across calls
     (``wshare``: one dict per shared kernel and forward pass, e.g. the RPN
@@ -612,7 +607,7 @@ def _shared_wino_release(wshare):
         wshare.pop("pending_bwd", None)
 
 
-def _wino_ws(B, H, W, D, OD, cin, cout, dev, dedicated=False):
+def _wino_ws(B, H, W, D, OD, cin, cout, dev):
     """(workspace, bytes) of one Winograd conv call, from the caching allocator.
     (A per-stream arena grown to the largest conv measured no better at 256^3 --
     216-940 ms before the side-stream throttle, DESIGN.md 5 -- and was removed.)"""
@@ -663,7 +658,7 @@ class BiasSums:
 
     def add(self, x, M, C, out):
         if any(o is out or o.data_ptr() == out.data_ptr() for _, _, _, o in self.items) \
-                or len(self.items) >= min(_lib.COL_SUMS_MAX, BIAS_BATCH_MAX):
+                or len(self.items) >= _lib.COL_SUMS_MAX:
             self.flush()
         self.items.append((x, M, C, out))
 
@@ -699,21 +694,18 @@ BIAS_BATCH = None
 # RPN heads' one sum alone: 29.9-30.0 ms) -- one reduction moved from the
 # backward to finish_backward is enough.
 BIAS_BATCHED = False
-# most items per batched launch (flushed when full; A/B of where the flushes land)
-BIAS_BATCH_MAX = 16
-# which bias-only units join the batch: the FPN convs ("fpn") and / or the RPN
-# class / bbox heads ("rpn")
-BIAS_BATCH_UNITS = "fpn+rpn"
 
 
 def bias_grad(dy, M, C, out, grads=None, batch=None):
     """out += column sums of dy [M, C]: batched when ``batch`` is armed and the
     unit has no bucket hook (a DP all-reduce may start as soon as the unit's
-    gradients are signalled done), inline otherwise."""
+    gradients are signalled done), inline otherwise.  Returns whether the sum
+    was deferred to the batch's flush."""
     if batch is not None and BIAS_BATCHED and not (grads and grads.get("_hook") is not None):
         batch.add(dy, M, C, out)
-    else:
-        bn_act_bwd(dy, None, None, M, C, False, None, None, None, None, None, None, None, out)
+        return True
+    bn_act_bwd(dy, None, None, M, C, False, None, None, None, None, None, None, None, out)
+    return False
 
 
 @dataclass
@@ -900,11 +892,416 @@ def _bn_fuse_ws(rec, B, H, W, D, C, dev):
     return torch.empty(n // 4 + 1, device=dev, dtype=torch.float32), n
 
 
+def _fused_handoff(rec, x, dx, launch):
+    """Apply the BN-ReLU backward of the unit that made x (``rec``, its BNFuse) in
+    this data gradient: ``launch(descriptor address, ws, ws_bytes)`` runs the fused
+    kernel (dx then holds the producer's dz).  Returns the extra elements it moves."""
+    B, H, W, D, C = x.shape
+    dres_f = torch.empty_like(x) if rec.need_res else None
+    bws, bwsb = _bn_fuse_ws(rec, B, H, W, D, C, x.device)
+    d = rec.descriptor(dres_f)
+    launch(ctypes.addressof(d), ptr(bws), bwsb)
+    rec.buf, rec.dres, rec.done = dx, dres_f, True
+    return x.numel() * (1 + (rec.z is not None) + rec.need_res)
+
+
+def _on_side(side):
+    """Context of a weight gradient's launches: the side stream if there is one."""
+    return torch.cuda.stream(side) if side is not None else contextlib.nullcontext()
+
+
+def _fwd_bn_affine(ctx, bn, grads, y):
+    """(scale, shift, z) of the unit's frozen BN (z: the pre-BN output, kept for the gamma gradient)."""
+    ctx.bn = ctx.aff_gen = None
+    if bn is None:
+        return None, None, None
+    gamma, beta, mean, var, eps = bn[:5]
+    aff = bn[5] if len(bn) > 5 else None
+    # the batched affine is a view into the store's shared buffer: the next
+    # refresh overwrites it (checked in backward, _check_generations)
+    ctx.aff_gen = bn[6] if len(bn) > 6 else None
+    if aff is None:
+        C = y.shape[-1]
+        aff = torch.empty((3, C), device=y.device, dtype=torch.float32)
+        check(_L().m3d_bn_affine(ptr(gamma), ptr(beta), ptr(mean), ptr(var), float(eps), C,
+                                 ptr(aff[1]), ptr(aff[2]), ptr(aff[0]), stream()), "bn_affine")
+    ctx.bn = (mean, aff[0], aff[1])
+    z = torch.empty_like(y) if grads is not None and grads.get("gamma") is not None else None
+    return aff[1], aff[2], z
+
+
+def _fwd_wino(ctx, x, w, pre, post, geo, grads, need_dx, pending, wshare):
+    """The Winograd forward: beside a depth slab the halo form (two phases around
+    a pending exchange), else on the pre-pass's weights (kv), keeping U (keep) or
+    plain / shared-workspace (v).  ``pre`` / ``post``: the epilogue's arguments.
+    Sets ctx.u, ctx.vd and the resolved ctx.halo; returns the engine."""
+    L = _L()
+    B, H, W, D, Cin = x.shape
+    Cout, OD, halo = w.shape[-1], geo.out[2], ctx.halo
+    dext = D + (halo[1] + halo[2] if halo is not None else 0)
+    ws, wsb = _wino_ws(B, H, W, dext, OD, Cin, Cout, x.device)
+    # training: keep the transformed input U for the weight gradient when
+    # the forward and weight-gradient tiles agree (u_bytes > 0)
+    keep = grads is not None and grads.get("kernel") is not None and min(Cin, Cout) >= WINO_WGRAD_MIN_C
+    nu = int(L.m3d_conv3d_wino_u_bytes(B, H, W, OD, Cin)) // 4 if keep else 0
+    if nu * 4 > WINO_KEEP_MAX_BYTES:
+        nu = 0          # too large to hold until the backward: the weight gradient re-transforms x
+    vf = None
+    if WINO_V_PREPASS and halo is None:
+        if WINO_V.active_fwd:
+            WINO_V.ensure(w, Cin, Cout, 0, 0)
+            vf = WINO_V.take(w, 0, 0)
+            if vf is not None:
+                torch.cuda.current_stream().wait_event(vf[1])
+        if need_dx and WINO_V.active_dgrad:
+            ty = _dgrad_tile_y(ctx.name)
+            WINO_V.ensure(w, Cin, Cout, 1, ty)
+            ctx.vd = WINO_V.take(w, 1, ty)      # waited on in the backward
+    ctx.u = torch.empty(nu, device=x.device, dtype=torch.float32) if nu > 0 else None
+    if halo is not None:
+        args = (B, H, W, D, Cin, ptr(w), Cout, *pre, *post, ptr(ctx.u), ptr(ws), wsb)
+        if pending is not None:
+            # phase 1 (weights + interior z tiles) overlaps the halo transfer
+            check(L.m3d_conv3d_fwd_wino_halo_phase(ptr(x), None, halo[1], halo[2], *args, 1, stream()),
+                  "conv3d_fwd_wino_halo_phase1")
+            halo = ctx.halo = pending.result()
+            check(L.m3d_conv3d_fwd_wino_halo_phase(ptr(x), ptr(halo[0]), halo[1], halo[2], *args, 2, stream()),
+                  "conv3d_fwd_wino_halo_phase2")
+        else:
+            check(L.m3d_conv3d_fwd_wino_halo(ptr(x), ptr(halo[0]), halo[1], halo[2], *args, stream()),
+                  "conv3d_fwd_wino_halo")
+        return "x3"
+    args = (ptr(x), B, H, W, D, Cin, ptr(w), Cout, OD, geo.pad[2], *pre, *post)
+    if vf is not None:
+        # the transformed weights from this forward's side-stream pre-pass (WinoVPrep)
+        check(L.m3d_conv3d_fwd_wino_kv(*args, ptr(ctx.u), ptr(vf[0]), ptr(ws), wsb, stream()), "conv3d_fwd_wino_kv")
+    elif ctx.u is not None:
+        check(L.m3d_conv3d_fwd_wino_keep(*args, ptr(ctx.u), ptr(ws), wsb, stream()), "conv3d_fwd_wino_keep")
+    else:
+        ws, wsb, v_ready = _shared_wino_ws(wshare, "fwd", ws, wsb, (w.data_ptr(), Cin, Cout))
+        check(L.m3d_conv3d_fwd_wino_v(*args, ptr(ws), wsb, v_ready, stream()), "conv3d_fwd_wino")
+    return "x3"
+
+
+def _fwd_direct(ctx, x, w, y, pre, post, geo, res_mode):
+    """Every other conv: the stem beside a depth slab (halo planes), a 1x1x1 conv as
+    one bf16-split GEMM (x3) or in K slices, else the implicit GEMM.  Returns the engine."""
+    L = _L()
+    B, H, W, D, Cin = x.shape
+    Cout, halo = w.shape[-1], ctx.halo
+    if halo is not None:
+        # the 7^3 stem on a depth slab: the neighbours' 3 planes beside the slab (no residual)
+        check(L.m3d_conv3d_fwd_halo(ptr(x), ptr(halo[0]), halo[1], halo[2], halo[0].shape[3] // 2, B, H, W, D, Cin,
+                                    ptr(w), *geo.k, Cout, *geo.out, *geo.stride, *geo.pad, *pre[:3], *post,
+                                    stream()), "conv3d_fwd_halo")
+    elif res_mode <= 2 and _conv1_x3(x.shape, geo, Cin, Cout):
+        planes = X3_PLANES.get(w, Cin, Cout, True)
+        X3_PLANES.ensure(w, Cin, Cout)
+        check(L.m3d_conv3d_fwd_x3(ptr(x), B, H, W, D, Cin, ptr(planes), Cout, *pre, res_mode, *post, stream()),
+              "conv3d_fwd_x3")
+        return "x3"
+    else:
+        nsk = _splitk(x.shape, geo, Cin, Cout, 0)
+        if nsk > 1:
+            wsk = torch.empty((nsk, y.numel()), device=x.device, dtype=torch.float32)
+            check(L.m3d_conv3d_fwd_splitk(ptr(x), B, H, W, D, Cin, ptr(w), Cout, *geo.out, *geo.stride, *pre,
+                                          res_mode, *post, nsk, ptr(wsk), wsk.numel() * 4, stream()),
+                  "conv3d_fwd_splitk")
+        else:
+            check(L.m3d_conv3d_fwd(ptr(x), B, H, W, D, Cin, ptr(w), *geo.k, Cout, *geo.out, *geo.stride, *geo.pad,
+                                   *pre, res_mode, *post, Cout, None, 0, 0, stream()), "conv3d_fwd")
+    return "f32"
+
+
+def _fwd_arm(ctx, x, w, y, z, has_bn, need_dx, wshare, fuse, fuse_in):
+    """The forward's hand-over to the backward: the shared workspace's pending count,
+    the data gradient's split planes, this unit's BNFuse (armed) and its producer's."""
+    geo, grads, halo = ctx.geo, ctx.grads, ctx.halo
+    Cin, Cout = x.shape[-1], w.shape[-1]
+    ctx.wshare = wshare
+    if wshare is not None and ctx.wino and halo is None and need_dx:
+        # data-gradient calls still to come: the last one releases the held workspace
+        wshare["pending_bwd"] = wshare.get("pending_bwd", 0) + 1
+    # the data gradient's split planes of this forward's refresh (X3Planes), if any
+    ctx.x3_bwd = None
+    if (geo.k == (1, 1, 1) and need_dx and halo is None
+            and _conv1_x3(x.shape, geo, Cout, Cin, bwd_data=True, fused=X3_BN_FUSE)):
+        ctx.x3_bwd = X3_PLANES.cached(w, False)
+        if ctx.x3_bwd is None:
+            X3_PLANES.ensure(w, Cin, Cout)
+    ctx.x3_gen = X3_PLANES.gen if ctx.x3_bwd is not None else None
+    ctx.bias_batch = BIAS_BATCH if grads is not None else None
+    # this unit's BN-ReLU backward handed to its consumer (BNFuse)
+    ctx.fuse = None
+    # (res_mode 2, the FPN's upsampled residual, has no fused form: its residual
+    # gradient needs the upsample adjoint, so such a unit is never armed)
+    if (fuse is not None and BN_FUSE and grads is not None and (has_bn or ctx.relu)
+            and Cout % 4 == 0 and ctx.res_mode in (0, 1)):
+        fuse.arm(y, z, ctx.bn, ctx.relu, ctx.res_mode != 0, grads, ctx.name)
+        ctx.fuse = fuse
+    # ... and the producer's, applied in this unit's data gradient
+    ctx.fuse_in = None
+    if (fuse_in is not None and fuse_in.armed and need_dx and halo is None and wshare is None
+            and fuse_in.y is not None and fuse_in.y.data_ptr() == x.data_ptr()
+            and fuse_in.y.shape == x.shape):
+        ctx.fuse_in = fuse_in
+
+
+def _bwd_own_bn(ctx, dy, y, z, grads, t0):
+    """(dz, dres) of the unit's own BN-ReLU backward: applied by its consumer's data
+    gradient already (BNFuse), trivial (no BN, no ReLU: the bias sums), or m3d_bn_act_bwd."""
+    Cout = dy.shape[-1]
+    M = dy.numel() // Cout
+    need_res = ctx.res_mode != 0
+    trivial = ctx.bn is None and not ctx.relu
+    rec, ctx.fuse = ctx.fuse, None
+    if rec is not None and rec.done:
+        # the consumer's data gradient already applied this unit's BN-ReLU
+        # backward: dy is its dz buffer, dres and the BN / bias sums are written
+        if rec.buf is None or dy.data_ptr() != rec.buf.data_ptr() or dy.shape != rec.buf.shape:
+            raise RuntimeError(f"{ctx.name}: fused BN-ReLU backward was applied by its consumer, but the "
+                               "output gradient has another contribution (the unit is not the consumer's "
+                               "sole producer-consumer pair; see nn.BNFuse)")
+        dres = rec.dres
+        rec.clear()
+        return dy, dres
+    if rec is not None:
+        rec.clear()
+    deferred = False
+    if trivial:
+        dz = dy
+        dres = dy if need_res else None
+        if grads.get("bias") is not None:
+            deferred = bias_grad(dy, M, Cout, grads["bias"], grads, ctx.bias_batch)
+    else:
+        dz = torch.empty_like(dy)
+        dres = torch.empty_like(dy) if need_res else None
+        mean, rstd, scale = ctx.bn if ctx.bn is not None else (None, None, None)
+        bn_act_bwd(dy, y, z, M, Cout, ctx.relu, scale, mean, rstd, dz, dres, grads.get("beta"),
+                   grads.get("gamma") if z is not None else None, grads.get("bias"))
+    if LAYER_LOG is not None and not deferred:      # (a deferred bias sum is logged by BiasSums.flush)
+        nel = dy.numel() * (1 + (0 if trivial else 1 + (ctx.relu or ctx.bn is not None) +
+                                 (z is not None) + (dres is not None)))
+        _log("bn_act_bwd", 0, 0, 4.0 * nel, "bwd_bn", ctx.name, t0)
+    return dz, dres
+
+
+def _wgrad_gemm(x, dz, dw, geo, halo):
+    """The implicit-GEMM weight gradient (beside a depth slab: reading the halo planes)."""
+    L = _L()
+    dims = (*x.shape, *geo.k, dz.shape[-1], *geo.out, *geo.stride, *geo.pad)
+    if halo is not None:
+        check(L.m3d_conv3d_bwd_weight_halo(ptr(x), ptr(halo[0]), halo[1], halo[2], halo[0].shape[3] // 2, ptr(dz),
+                                           *dims, ptr(dw), stream()), "conv3d_bwd_weight_halo")
+    else:
+        check(L.m3d_conv3d_bwd_weight(ptr(x), ptr(dz), *dims, ptr(dw), stream()), "conv3d_bwd_weight")
+
+
+def _wino_wgrad(ctx, x, dz, w, dw, side, direct):
+    """Weight gradient of a Winograd unit: the implicit GEMM below WINO_WGRAD_MIN_C
+    channels, else in the Winograd domain on the kept U, the slab's halo planes, or x."""
+    L = _L()
+    B, H, W, D, Cin = x.shape
+    Cout, geo, halo = w.shape[-1], ctx.geo, ctx.halo
+    OH, OW, OD = geo.out
+    with _on_side(side):
+        tw = _span()
+        small = min(Cin, Cout) < WINO_WGRAD_MIN_C
+        if small:
+            _wgrad_gemm(x, dz, dw, geo, halo)
+        else:
+            dext = D + (halo[1] + halo[2] if halo is not None else 0)
+            wsw, wswb = _wino_ws(B, H, W, dext, OD, Cin, Cout, x.device)
+            if ctx.u is not None:
+                ctx.u.record_stream(torch.cuda.current_stream())
+                check(L.m3d_conv3d_bwd_weight_wino_u(ptr(ctx.u), ptr(dz), B, H, W, D, Cin, Cout, OD, geo.pad[2],
+                                                     ptr(dw), ptr(wsw), wswb, stream()), "conv3d_bwd_weight_wino_u")
+            elif halo is not None:
+                check(L.m3d_conv3d_bwd_weight_wino_halo(ptr(x), ptr(halo[0]), halo[1], halo[2], ptr(dz), B, H, W, D,
+                                                        Cin, Cout, ptr(dw), ptr(wsw), wswb, stream()),
+                      "conv3d_bwd_weight_wino_halo")
+            else:
+                check(L.m3d_conv3d_bwd_weight_wino(ptr(x), ptr(dz), B, H, W, D, Cin, Cout, OD, geo.pad[2],
+                                                   ptr(dw), ptr(wsw), wswb, stream()), "conv3d_bwd_weight_wino")
+        if LAYER_LOG is not None:
+            exe = direct if small else \
+                _wino_exec(B, OH, OW, OD, Cin, Cout, int(L.m3d_conv3d_wino_wgrad_tile_z()))
+            _log("wino_wgrad", direct, exe, 4.0 * (x.numel() + dz.numel() + w.numel()), "bwd_weight", ctx.name, tw,
+                 "f32" if small else "x3")
+    ctx.u = None
+
+
+def _wino_dgrad(ctx, x, dz, w, direct):
+    """Data gradient of a Winograd unit: the slab's halo form, else on the pre-pass's
+    weights (xv) or plain / shared-workspace (vy), each fused with the producer's
+    BN-ReLU backward where ctx.fuse_in allows.  Returns dx (None when parked)."""
+    L = _L()
+    B, H, W, D, Cin = x.shape
+    Cout, geo, halo = w.shape[-1], ctx.geo, ctx.halo
+    OH, OW, OD = geo.out
+    td = _span()
+    dext = D + (halo[1] + halo[2] if halo is not None else 0)
+    ws, wsb = _wino_ws(B, H, W, dext, OD, Cin, Cout, x.device)
+    dx, acc = _link_take(ctx.link, x)
+    if dx is None:
+        dx = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    fused_nel = 0
+    if halo is not None:
+        ty = 0
+        dh = torch.empty_like(halo[0])
+        check(L.m3d_conv3d_bwd_data_wino_halo(ptr(dz), ptr(w), halo[1], halo[2], B, H, W, D, Cin, Cout, ptr(dx),
+                                              ptr(dh), acc, ptr(ws), wsb, stream()), "conv3d_bwd_data_wino_halo")
+        slab.return_halo_grads(dx, dh)
+    else:
+        ty = _dgrad_tile_y(ctx.name)
+        vd = ctx.vd                     # the forward pre-pass's data-gradient transform (WinoVPrep)
+        if vd is not None:
+            if vd[2] != WINO_V.gen:
+                raise RuntimeError(f"{ctx.name}: conv backward after another model forward: the "
+                                   "pre-transformed Winograd weights were refreshed (run each backward "
+                                   "before the next forward)")
+            torch.cuda.current_stream().wait_event(vd[1])
+        else:
+            ws, wsb, v_ready = _shared_wino_ws(ctx.wshare, "bwd", ws, wsb, (w.data_ptr(), Cin, Cout, ty))
+        args = (ptr(dz), ptr(w), B, H, W, D, Cin, Cout, OD, geo.pad[2], ptr(dx), acc, ptr(ws), wsb)
+        rec = ctx.fuse_in
+        if (rec is not None and rec.armed and (Cin % 256 == 0 or 256 % Cin == 0)
+                and not _per_item(B, H * W * max(D, OD), max(Cin, Cout), 0, 0)
+                and _fuse_final(ctx.link, x, acc)):
+            if vd is not None:
+                fused_nel = _fused_handoff(rec, x, dx, lambda d, bws, bwsb: check(
+                    L.m3d_conv3d_bwd_data_wino_xv(*args, ptr(vd[0]), ty, d, bws, bwsb, stream()),
+                    "conv3d_bwd_data_wino_xv(bn)"))
+            else:
+                fused_nel = _fused_handoff(rec, x, dx, lambda d, bws, bwsb: check(
+                    L.m3d_conv3d_bwd_data_wino_bny(*args, v_ready, d, bws, bwsb, ty, stream()),
+                    "conv3d_bwd_data_wino_bn"))
+        elif vd is not None:
+            check(L.m3d_conv3d_bwd_data_wino_xv(*args, ptr(vd[0]), ty, None, None, 0, stream()),
+                  "conv3d_bwd_data_wino_xv")
+        else:
+            check(L.m3d_conv3d_bwd_data_wino_vy(*args, v_ready, ty, stream()), "conv3d_bwd_data_wino")
+        _shared_wino_release(ctx.wshare)
+    if LAYER_LOG is not None:
+        _log("wino_dgrad", direct, _wino_exec(B, OH, OW, OD, Cin, Cout, int(L.m3d_conv3d_wino_dgrad_tile_z()),
+                                              ty or int(L.m3d_conv3d_wino_dgrad_tile_y())),
+             4.0 * (dz.numel() + w.numel() + x.numel() * (1 + acc) + fused_nel), "bwd_data", ctx.name, td, "x3")
+    return _link_park(ctx.link, dx, acc)
+
+
+def _direct_wgrad(ctx, x, dz, w, dw, side, direct):
+    """Weight gradient of a direct unit: the implicit GEMM (the library runs the convs
+    _wgrad1_x3 names on the split GEMM); the stage-first blocks' (2,2,1)-strided 1x1x1
+    convs reach that split GEMM through their input rows gathered once."""
+    L = _L()
+    B, H, W, D, Cin = x.shape
+    Cout, geo, halo = w.shape[-1], ctx.geo, ctx.halo
+    OH, OW, OD = geo.out
+    nb = 4.0 * (x.numel() + dz.numel() + w.numel())
+    with _on_side(side):
+        tw = _span()
+        if (WGRAD1_STRIDED_X3 and halo is None and geo.stride == (2, 2, 1)
+                and (OH, OW, OD) == ((H + 1) // 2, (W + 1) // 2, D)):
+            sub = ConvGeom(geo.k, (1, 1, 1), geo.pad, geo.out)      # the conv of x[:, ::2, ::2]
+            if _wgrad1_x3(sub, Cin, Cout, geo.out):
+                xs = torch.empty((B, OH, OW, OD, Cin), device=x.device, dtype=torch.float32)
+                check(L.m3d_subsample221_fwd(ptr(x), B, H, W, D, Cin, ptr(xs), stream()), "subsample221")
+                x, geo = xs, sub
+        _wgrad_gemm(x, dz, dw, geo, halo)       # (halo: the stem on a depth slab)
+        if LAYER_LOG is not None:
+            _log(f"conv{geo.k[0]}_wgrad", direct, direct, nb, "bwd_weight", ctx.name, tw,
+                 "x3" if halo is None and _wgrad1_x3(geo, Cin, Cout, x.shape[1:4]) else "f32")
+
+
+def _direct_dgrad(ctx, x, dz, w, direct):
+    """Data gradient of a direct unit (dx = parked gradient + conv^T dz; None when
+    parked): a 1x1x1 conv on the bf16-split GEMM, else split-K or the implicit GEMM,
+    each fused with the producer's BN-ReLU backward where ctx.fuse_in allows."""
+    L = _L()
+    B, H, W, D, Cin = x.shape
+    Cout, geo, link, rec = w.shape[-1], ctx.geo, ctx.link, ctx.fuse_in
+    kh, kw, kd = geo.k
+    OH, OW, OD = geo.out
+    td = _span()
+    fused_nel = 0
+    strided = any(s != 1 for s in geo.stride)
+    dx, acc = _link_take(link, x)
+    if dx is None:
+        dx = (torch.zeros if strided else torch.empty)(x.shape, device=x.device, dtype=torch.float32)
+    wd, dzd, cpad = w, dz, Cout
+    if Cout % 32:   # bwd-data stages 32-channel slices of dz: zero-pad the channel dim
+        cpad = -(-Cout // 32) * 32
+        wd = torch.zeros((kh, kw, kd, Cin, cpad), device=w.device, dtype=torch.float32)
+        wd[..., :Cout] = w
+        dzd = torch.zeros((B, OH, OW, OD, cpad), device=dz.device, dtype=torch.float32)
+        dzd[..., :Cout] = dz
+    nsk = _splitk(x.shape, geo, Cin, cpad, 1)
+    x3 = cpad == Cout and not acc and _conv1_x3(x.shape, geo, Cout, Cin, bwd_data=True)
+    # (the fused split GEMM takes no accumulating gradient: neutral when it did, CONV1_X3_DGRAD_FUSED_MIN_K)
+    x3_fused = (cpad == Cout and X3_BN_FUSE and rec is not None and rec.armed and not acc
+                and _conv1_x3(x.shape, geo, Cout, Cin, bwd_data=True, fused=True) and _fuse_final(link, x, acc))
+    if x3 or x3_fused:
+        planes = ctx.x3_bwd if ctx.x3_bwd is not None else X3_PLANES.get(w, Cin, Cout, False)
+        if x3_fused:
+            # the producer's BN-ReLU backward in the split GEMM's epilogue
+            fused_nel = _fused_handoff(rec, x, dx, lambda d, bws, bwsb: check(
+                L.m3d_conv3d_bwd_data_x3_bna(ptr(dz), ptr(planes), B, H, W, D, Cin, Cout, ptr(dx), acc, d, bws, bwsb,
+                                             stream()), "conv3d_bwd_data_x3_bna"))
+        else:
+            check(L.m3d_conv3d_bwd_data_x3(ptr(dz), ptr(planes), B, H, W, D, Cin, Cout, ptr(dx), stream()),
+                  "conv3d_bwd_data_x3")
+    else:
+        fuse = (rec is not None and rec.armed and not strided and (OH, OW, OD) == (H, W, D)
+                and not _per_item(B, H * W * D, Cin, OH * OW * OD, cpad) and _fuse_final(link, x, acc))
+        if nsk > 1:
+            wsk = torch.empty((nsk, B * OH * OW * OD * Cin), device=x.device, dtype=torch.float32)
+            if fuse:
+                fused_nel = _fused_handoff(rec, x, dx, lambda d, bws, bwsb: check(
+                    L.m3d_conv3d_bwd_data_splitk_bn(ptr(dzd), ptr(wd), B, H, W, D, Cin, cpad, ptr(dx), acc, nsk,
+                                                    ptr(wsk), wsk.numel() * 4, d, bws, bwsb, stream()),
+                    "conv3d_bwd_data_splitk_bn"))
+            else:
+                check(L.m3d_conv3d_bwd_data_splitk(ptr(dzd), ptr(wd), B, H, W, D, Cin, cpad, OH, OW, OD, *geo.stride,
+                                                   ptr(dx), acc, nsk, ptr(wsk), wsk.numel() * 4, stream()),
+                      "conv3d_bwd_data_splitk")
+        else:
+            args = (ptr(dzd), ptr(wd), B, H, W, D, Cin, kh, kw, kd, cpad, OH, OW, OD, *geo.stride, *geo.pad, ptr(dx),
+                    acc)
+            if fuse:
+                fused_nel = _fused_handoff(rec, x, dx, lambda d, bws, bwsb: check(
+                    L.m3d_conv3d_bwd_data_bn(*args, d, bws, bwsb, stream()), "conv3d_bwd_data_bn"))
+            else:
+                check(L.m3d_conv3d_bwd_data(*args, stream()), "conv3d_bwd_data")
+    if LAYER_LOG is not None:
+        _log(f"conv{kh}_dgrad", direct, direct, 4.0 * (dz.numel() + w.numel() + x.numel() * (1 + acc) + fused_nel),
+             "bwd_data", ctx.name, td, "x3" if x3 or x3_fused else "f32")
+    return _link_park(link, dx, acc)
+
+
+def _residual_grad(ctx, dres):
+    """The residual's gradient: parked on the identity block's GradLink (a direct unit's),
+    returned as it is, or (the FPN's (2,2,1)-nearest residual) upsampled back."""
+    link = ctx.link
+    if (ctx.res_mode == 1 and not ctx.wino and link is not None and link.mode == "res"
+            and (ctx.bn is not None or ctx.relu)):
+        link.buf = dres                               # consumed by the input conv's backward
+        return None
+    if ctx.res_mode != 2:
+        return dres                                   # (None without a residual)
+    rb, rh, rw, rd, rc = ctx.res_shape
+    tu = _span()
+    dr = torch.empty(ctx.res_shape, device=dres.device, dtype=torch.float32)
+    check(_L().m3d_upsample221_bwd(ptr(dres), rb, rh, rw, rd, rc, ptr(dr), 0, stream()), "upsample221_bwd")
+    _log("upsample_bwd", 0, 0, 4.0 * (dres.numel() + dr.numel()), "bwd_data", ctx.name, tu)
+    return dr
+
+
 class _ConvBNAct(torch.autograd.Function):
     """y = act(BN_frozen(conv(x, w) + b) [+ residual]).
 
     res_mode 1: residual has y's shape; 2: residual is the (2,2,1)-nearest
-    source of y (FPN top-down add, core/models.py:3193-3204)."""
+    source of y (FPN top-down add, core/models.py:3193-3204).  forward and
+    backward only order the launch functions above, which hold the routing."""
 
     @staticmethod
     def forward(ctx, x, residual, w, b, bn, geo, relu, res_mode, grads, need_dx, link=None, halo=None,
@@ -915,163 +1312,34 @@ class _ConvBNAct(torch.autograd.Function):
         # depth slab (m3d.slab): halo = (planes [B,H,W,2,C], has_lo, has_hi) read by the
         # Winograd kernels beside x instead of a halo-extended copy of x; a
         # slab.PendingHalo (exchange still in flight) is resolved between the two
-        # launch phases of the Winograd conv below
+        # launch phases of the Winograd conv (_fwd_wino)
         pending = halo if isinstance(halo, slab.PendingHalo) else None
         if pending is not None:
             halo = (None, pending.has_lo, pending.has_hi)
         ctx.halo = halo
-        kh, kw, kd = geo.k
         Cout = w.shape[-1]
-        OH, OW, OD = geo.out
-        y = torch.empty((B, OH, OW, OD, Cout), device=x.device, dtype=torch.float32)
-        z = None
-        scale = shift = None
-        if bn is not None:
-            gamma, beta, mean, var, eps = bn[:5]
-            aff = bn[5] if len(bn) > 5 else None
-            # the batched affine is a view into the store's shared buffer: the next
-            # refresh overwrites it (checked in backward, _check_generations)
-            ctx.aff_gen = bn[6] if len(bn) > 6 else None
-            if aff is None:
-                aff = torch.empty((3, Cout), device=x.device, dtype=torch.float32)
-                check(_L().m3d_bn_affine(ptr(gamma), ptr(beta), ptr(mean), ptr(var), float(eps), Cout,
-                                         ptr(aff[1]), ptr(aff[2]), ptr(aff[0]), stream()), "bn_affine")
-            rstd, scale, shift = aff[0], aff[1], aff[2]
-            if grads is not None and grads.get("gamma") is not None:
-                z = torch.empty_like(y)
-            ctx.bn = (mean, rstd, scale)
-        else:
-            ctx.bn = None
-            ctx.aff_gen = None
+        y = torch.empty((B, *geo.out, Cout), device=x.device, dtype=torch.float32)
+        scale, shift, z = _fwd_bn_affine(ctx, bn, grads, y)
         ctx.wino = use_winograd(geo, Cin, Cout, (H, W, D)) and res_mode != 2
-        ctx.vd = None
         if halo is not None and not ctx.wino and not _stem_halo(geo, Cin, Cout, res_mode):
             raise ValueError("halo planes are read by the Winograd kernels and the stem only")
-        ctx.u = None
-        if halo is not None and not ctx.wino:
-            # the 7^3 stem on a depth slab: the neighbours' 3 planes beside the slab
-            r = halo[0].shape[3] // 2
-            check(_L().m3d_conv3d_fwd_halo(ptr(x), ptr(halo[0]), halo[1], halo[2], r, B, H, W, D, Cin, ptr(w),
-                                           kh, kw, kd, Cout, OH, OW, OD, *geo.stride, *geo.pad, ptr(b),
-                                           ptr(scale), ptr(shift), 1 if relu else 0, ptr(z), ptr(y), stream()),
-                  "conv3d_fwd_halo")
-        elif ctx.wino:
-            dext = D + (halo[1] + halo[2] if halo is not None else 0)
-            ws, wsb = _wino_ws(B, H, W, dext, OD, Cin, Cout, x.device)
-            # training: keep the transformed input U for the weight gradient when
-            # the forward and weight-gradient tiles agree (u_bytes > 0)
-            nu = int(_L().m3d_conv3d_wino_u_bytes(B, H, W, OD, Cin)) // 4 \
-                if grads is not None and grads.get("kernel") is not None \
-                and min(Cin, Cout) >= WINO_WGRAD_MIN_C else 0
-            if nu * 4 > WINO_KEEP_MAX_BYTES:
-                nu = 0          # too large to hold until the backward: the weight gradient re-transforms x
-            vf = None
-            ctx.vd = None
-            if WINO_V_PREPASS and halo is None:
-                if WINO_V.active_fwd:
-                    WINO_V.ensure(w, Cin, Cout, 0, 0)
-                    vf = WINO_V.take(w, 0, 0)
-                    if vf is not None:
-                        torch.cuda.current_stream().wait_event(vf[1])
-                if need_dx and WINO_V.active_dgrad:
-                    ty = _dgrad_tile_y(name)
-                    WINO_V.ensure(w, Cin, Cout, 1, ty)
-                    ctx.vd = WINO_V.take(w, 1, ty)      # waited on in the backward
-            if pending is not None:
-                # phase 1 (weights + interior z tiles) overlaps the halo transfer
-                ctx.u = torch.empty(nu, device=x.device, dtype=torch.float32) if nu > 0 else None
-                args = (B, H, W, D, Cin, ptr(w), Cout, ptr(b), ptr(scale), ptr(shift), ptr(residual),
-                        1 if relu else 0, ptr(z), ptr(y), ptr(ctx.u), ptr(ws), wsb)
-                check(_L().m3d_conv3d_fwd_wino_halo_phase(ptr(x), None, halo[1], halo[2], *args, 1, stream()),
-                      "conv3d_fwd_wino_halo_phase1")
-                halo = ctx.halo = pending.result()
-                check(_L().m3d_conv3d_fwd_wino_halo_phase(ptr(x), ptr(halo[0]), halo[1], halo[2], *args, 2,
-                                                          stream()), "conv3d_fwd_wino_halo_phase2")
-            elif halo is not None:
-                ctx.u = torch.empty(nu, device=x.device, dtype=torch.float32) if nu > 0 else None
-                check(_L().m3d_conv3d_fwd_wino_halo(ptr(x), ptr(halo[0]), halo[1], halo[2], B, H, W, D, Cin,
-                                                    ptr(w), Cout, ptr(b), ptr(scale), ptr(shift), ptr(residual),
-                                                    1 if relu else 0, ptr(z), ptr(y), ptr(ctx.u), ptr(ws), wsb,
-                                                    stream()), "conv3d_fwd_wino_halo")
-            elif vf is not None:
-                # the transformed weights from this forward's side-stream pre-pass (WinoVPrep)
-                ctx.u = torch.empty(nu, device=x.device, dtype=torch.float32) if nu > 0 else None
-                check(_L().m3d_conv3d_fwd_wino_kv(ptr(x), B, H, W, D, Cin, ptr(w), Cout, OD, geo.pad[2],
-                                                  ptr(b), ptr(scale), ptr(shift), ptr(residual), 1 if relu else 0,
-                                                  ptr(z), ptr(y), ptr(ctx.u), ptr(vf[0]), ptr(ws), wsb, stream()),
-                      "conv3d_fwd_wino_kv")
-            elif nu > 0:
-                ctx.u = torch.empty(nu, device=x.device, dtype=torch.float32)
-                check(_L().m3d_conv3d_fwd_wino_keep(ptr(x), B, H, W, D, Cin, ptr(w), Cout, OD, geo.pad[2],
-                                                    ptr(b), ptr(scale), ptr(shift), ptr(residual),
-                                                    1 if relu else 0, ptr(z), ptr(y), ptr(ctx.u),
-                                                    ptr(ws), wsb, stream()), "conv3d_fwd_wino_keep")
-            else:
-                if wshare is not None:          # may be held across calls: not the arena
-                    ws, wsb = _wino_ws(B, H, W, dext, OD, Cin, Cout, x.device, dedicated=True)
-                ws, wsb, v_ready = _shared_wino_ws(wshare, "fwd", ws, wsb, (w.data_ptr(), Cin, Cout))
-                check(_L().m3d_conv3d_fwd_wino_v(ptr(x), B, H, W, D, Cin, ptr(w), Cout, OD, geo.pad[2],
-                                                 ptr(b), ptr(scale), ptr(shift), ptr(residual), 1 if relu else 0,
-                                                 ptr(z), ptr(y), ptr(ws), wsb, v_ready, stream()),
-                      "conv3d_fwd_wino")
-        elif res_mode <= 2 and _conv1_x3(x.shape, geo, Cin, Cout):
-            planes = _x3_planes(w, Cin, Cout, True)
-            X3_PLANES.ensure(w, Cin, Cout)
-            check(_L().m3d_conv3d_fwd_x3(ptr(x), B, H, W, D, Cin, ptr(planes), Cout, ptr(b), ptr(scale),
-                                         ptr(shift), ptr(residual), res_mode, 1 if relu else 0, ptr(z), ptr(y),
-                                         stream()), "conv3d_fwd_x3")
-        else:
-            nsk = _splitk(x.shape, geo, Cin, Cout, 0)
-            if nsk > 1:
-                wsk = torch.empty((nsk, y.numel()), device=x.device, dtype=torch.float32)
-                check(_L().m3d_conv3d_fwd_splitk(ptr(x), *x.shape, ptr(w), Cout, OH, OW, OD, *geo.stride,
-                                                 ptr(b), ptr(scale), ptr(shift), ptr(residual), res_mode,
-                                                 1 if relu else 0, ptr(z), ptr(y), nsk, ptr(wsk),
-                                                 wsk.numel() * 4, stream()), "conv3d_fwd_splitk")
-            else:
-                check(_L().m3d_conv3d_fwd(ptr(x), *x.shape, ptr(w), *geo.k, Cout, OH, OW, OD,
-                                          *geo.stride, *geo.pad, ptr(b), ptr(scale), ptr(shift),
-                                          ptr(residual), res_mode, 1 if relu else 0, ptr(z), ptr(y), Cout,
-                                          None, 0, 0, stream()), "conv3d_fwd")
-        if LAYER_LOG is not None:
-            direct = 2.0 * (y.numel() // Cout) * kh * kw * kd * Cin * Cout
-            exe = direct
-            if ctx.wino:
-                exe = _wino_exec(B, OH, OW, OD, Cin, Cout, int(_L().m3d_conv3d_wino_tile_z()))
-            nb = 4.0 * (x.numel() + w.numel() + y.numel() + (residual.numel() if residual is not None else 0))
-            x3 = ctx.wino or (res_mode <= 2 and halo is None and _conv1_x3(x.shape, geo, Cin, Cout))
-            _log("wino" if ctx.wino else f"conv{kh}", direct, exe, nb, "fwd", name, t0, "x3" if x3 else "f32")
-        ctx.save_for_backward(x, w, y, z)
-        ctx.wshare = wshare
-        if wshare is not None and ctx.wino and halo is None and need_dx:
-            # data-gradient calls still to come: the last one releases the held workspace
-            wshare["pending_bwd"] = wshare.get("pending_bwd", 0) + 1
-        ctx.geo, ctx.relu, ctx.res_mode, ctx.grads, ctx.need_dx = geo, relu, res_mode, grads, need_dx
-        # the data gradient's split planes of this forward's refresh (X3Planes), if any
-        ctx.x3_bwd = None
-        if (geo.k == (1, 1, 1) and need_dx and halo is None
-                and _conv1_x3(x.shape, geo, Cout, Cin, bwd_data=True, fused=X3_BN_FUSE)):
-            ctx.x3_bwd = X3_PLANES.cached(w, False)
-            if ctx.x3_bwd is None:
-                X3_PLANES.ensure(w, Cin, Cout)
-        ctx.x3_gen = X3_PLANES.gen if ctx.x3_bwd is not None else None
-        ctx.bias_batch = BIAS_BATCH if grads is not None else None
-        ctx.link = link
+        ctx.u = ctx.vd = None
+        ctx.geo, ctx.relu, ctx.res_mode, ctx.grads, ctx.need_dx, ctx.link = geo, relu, res_mode, grads, need_dx, link
         ctx.res_shape = None if residual is None else tuple(residual.shape)
-        # this unit's BN-ReLU backward handed to its consumer (BNFuse)
-        ctx.fuse = None
-        # (res_mode 2, the FPN's upsampled residual, has no fused form: its residual
-        # gradient needs the upsample adjoint, so such a unit is never armed)
-        if (fuse is not None and BN_FUSE and grads is not None and (bn is not None or relu)
-                and Cout % 4 == 0 and res_mode in (0, 1)):
-            fuse.arm(y, z, ctx.bn, relu, res_mode != 0, grads, name)
-            ctx.fuse = fuse
-        # ... and the producer's, applied in this unit's data gradient
-        ctx.fuse_in = None
-        if (fuse_in is not None and fuse_in.armed and need_dx and halo is None and wshare is None
-                and fuse_in.y is not None and fuse_in.y.data_ptr() == x.data_ptr()
-                and fuse_in.y.shape == x.shape):
-            ctx.fuse_in = fuse_in
+        pre = (ptr(b), ptr(scale), ptr(shift), ptr(residual))
+        post = (1 if relu else 0, ptr(z), ptr(y))
+        if ctx.wino:
+            engine = _fwd_wino(ctx, x, w, pre, post, geo, grads, need_dx, pending, wshare)
+        else:
+            engine = _fwd_direct(ctx, x, w, y, pre, post, geo, res_mode)
+        if LAYER_LOG is not None:
+            kh, kw, kd = geo.k
+            direct = 2.0 * (y.numel() // Cout) * kh * kw * kd * Cin * Cout
+            exe = _wino_exec(B, *geo.out, Cin, Cout, int(_L().m3d_conv3d_wino_tile_z())) if ctx.wino else direct
+            nb = 4.0 * (x.numel() + w.numel() + y.numel() + (residual.numel() if residual is not None else 0))
+            _log("wino" if ctx.wino else f"conv{kh}", direct, exe, nb, "fwd", name, t0, engine)
+        ctx.save_for_backward(x, w, y, z)
+        _fwd_arm(ctx, x, w, y, z, bn is not None, need_dx, wshare, fuse, fuse_in)
         return y
 
     @staticmethod
@@ -1079,298 +1347,29 @@ class _ConvBNAct(torch.autograd.Function):
         _check_generations(ctx)
         x, w, y, z = ctx.saved_tensors
         dy = dy.contiguous()
-        geo, grads = ctx.geo, ctx.grads or {}
-        B, H, W, D, Cin = x.shape
-        kh, kw, kd = geo.k
-        Cout = w.shape[-1]
-        OH, OW, OD = geo.out
-        M = B * OH * OW * OD
-        L = _L()
-        need_res = ctx.res_mode != 0
-        trivial = ctx.bn is None and not ctx.relu
-        logging = LAYER_LOG is not None
-        direct = 2.0 * M * kh * kw * kd * Cin * Cout
-        t0 = _span()
-        rec = ctx.fuse
-        ctx.fuse = None
-        fused_bn = rec is not None and rec.done
-        if fused_bn:
-            # the consumer's data gradient already applied this unit's BN-ReLU
-            # backward: dy is its dz buffer, dres and the BN / bias sums are written
-            if rec.buf is None or dy.data_ptr() != rec.buf.data_ptr() or dy.shape != rec.buf.shape:
-                raise RuntimeError(f"{ctx.name}: fused BN-ReLU backward was applied by its consumer, but the "
-                                   "output gradient has another contribution (the unit is not the consumer's "
-                                   "sole producer-consumer pair; see nn.BNFuse)")
-            dz = dy
-            dres = rec.dres
-            rec.clear()
-        elif trivial:
-            if rec is not None:
-                rec.clear()
-            dz = dy
-            dres = dy if need_res else None
-            if grads.get("bias") is not None:
-                bias_grad(dy, M, Cout, grads["bias"], grads,
-                          ctx.bias_batch if "fpn" in BIAS_BATCH_UNITS.split("+") else None)
-        else:
-            if rec is not None:
-                rec.clear()
-            dz = torch.empty_like(dy)
-            dres = torch.empty_like(dy) if need_res else None
-            mean = rstd = scale = None
-            if ctx.bn is not None:
-                mean, rstd, scale = ctx.bn
-            bn_act_bwd(dy, y, z, M, Cout, ctx.relu, scale, mean, rstd, dz, dres, grads.get("beta"),
-                       grads.get("gamma") if z is not None else None, grads.get("bias"))
-        if logging and not fused_bn and not (trivial and ctx.bias_batch is not None and BIAS_BATCHED
-                                             and grads.get("_hook") is None):
-            nel = dy.numel() * (1 + (0 if trivial else 1 + (ctx.relu or ctx.bn is not None) +
-                                     (z is not None) + (dres is not None and not trivial)))
-            _log("bn_act_bwd", 0, 0, 4.0 * nel, "bwd_bn", ctx.name, t0)
-        side = _wgrad_stream(x.device) if grads.get("kernel") is not None else None
+        grads = ctx.grads or {}
+        direct = 2.0 * dy.numel() * ctx.geo.k[0] * ctx.geo.k[1] * ctx.geo.k[2] * x.shape[-1]
+        dz, dres = _bwd_own_bn(ctx, dy, y, z, grads, _span())
+        dw = grads.get("kernel")
+        side = _wgrad_stream(x.device) if dw is not None else None
+        halo = ctx.halo
         if side is not None:
             dz.record_stream(side)
             x.record_stream(side)
-        halo = ctx.halo
-        dext = D + (halo[1] + halo[2] if halo is not None else 0)
-        if halo is not None and side is not None:
-            halo[0].record_stream(side)
-        if ctx.wino:
-            def wgrad():
-                with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
-                    tw = _span()
-                    if min(Cin, Cout) < WINO_WGRAD_MIN_C and halo is not None:
-                        # the direct kernel reads the neighbours' planes beside the slab
-                        check(L.m3d_conv3d_bwd_weight_halo(ptr(x), ptr(halo[0]), halo[1], halo[2], 1, ptr(dz),
-                                                           B, H, W, D, Cin, kh, kw, kd, Cout, OH, OW, OD,
-                                                           *geo.stride, *geo.pad, ptr(grads["kernel"]), stream()),
-                              "conv3d_bwd_weight_halo")
-                    elif min(Cin, Cout) < WINO_WGRAD_MIN_C:
-                        check(L.m3d_conv3d_bwd_weight(ptr(x), ptr(dz), B, H, W, D, Cin, kh, kw, kd,
-                                                      Cout, OH, OW, OD, *geo.stride, *geo.pad,
-                                                      ptr(grads["kernel"]), stream()), "conv3d_bwd_weight")
-                    elif halo is not None and ctx.u is None:
-                        wsw, wswb = _wino_ws(B, H, W, dext, OD, Cin, Cout, x.device)
-                        check(L.m3d_conv3d_bwd_weight_wino_halo(ptr(x), ptr(halo[0]), halo[1], halo[2], ptr(dz),
-                                                                B, H, W, D, Cin, Cout, ptr(grads["kernel"]),
-                                                                ptr(wsw), wswb, stream()),
-                              "conv3d_bwd_weight_wino_halo")
-                    else:
-                        wsw, wswb = _wino_ws(B, H, W, dext, OD, Cin, Cout, x.device)
-                        if ctx.u is not None:
-                            ctx.u.record_stream(torch.cuda.current_stream())
-                            check(L.m3d_conv3d_bwd_weight_wino_u(ptr(ctx.u), ptr(dz), B, H, W, D, Cin, Cout,
-                                                                 OD, geo.pad[2], ptr(grads["kernel"]),
-                                                                 ptr(wsw), wswb, stream()),
-                                  "conv3d_bwd_weight_wino_u")
-                        else:
-                            check(L.m3d_conv3d_bwd_weight_wino(ptr(x), ptr(dz), B, H, W, D, Cin, Cout, OD,
-                                                               geo.pad[2], ptr(grads["kernel"]), ptr(wsw),
-                                                               wswb, stream()),
-                                  "conv3d_bwd_weight_wino")
-                    if logging:
-                        exe = direct if min(Cin, Cout) < WINO_WGRAD_MIN_C else \
-                            _wino_exec(B, OH, OW, OD, Cin, Cout, int(L.m3d_conv3d_wino_wgrad_tile_z()))
-                        _log("wino_wgrad", direct, exe, 4.0 * (x.numel() + dz.numel() + w.numel()),
-                             "bwd_weight", ctx.name, tw, "f32" if min(Cin, Cout) < WINO_WGRAD_MIN_C else "x3")
-                ctx.u = None
-            has_w = grads.get("kernel") is not None
-            if has_w and not WGRAD_LAST:
-                wgrad()
-            td = _span()
-            ws, wsb = _wino_ws(B, H, W, dext, OD, Cin, Cout, x.device)
-            dx = None
-            fused_nel = 0
-            if ctx.need_dx:
-                dx, acc = _link_take(ctx.link, x)
-                if dx is None:
-                    dx = torch.empty(x.shape, device=x.device, dtype=torch.float32)
-                ty = 0 if halo is not None else _dgrad_tile_y(ctx.name)
-                if halo is not None:
-                    dh = torch.empty_like(halo[0])
-                    check(L.m3d_conv3d_bwd_data_wino_halo(ptr(dz), ptr(w), halo[1], halo[2], B, H, W, D, Cin,
-                                                          Cout, ptr(dx), ptr(dh), acc, ptr(ws), wsb, stream()),
-                          "conv3d_bwd_data_wino_halo")
-                    slab.return_halo_grads(dx, dh)
-                else:
-                    vd = ctx.vd                     # the forward pre-pass's data-gradient transform (WinoVPrep)
-                    if vd is not None:
-                        if vd[2] != WINO_V.gen:
-                            raise RuntimeError(f"{ctx.name}: conv backward after another model forward: the "
-                                               "pre-transformed Winograd weights were refreshed (run each backward "
-                                               "before the next forward)")
-                        torch.cuda.current_stream().wait_event(vd[1])
-                        v_ready = 0
-                    else:
-                        if ctx.wshare is not None:      # may be held across calls: not the arena
-                            ws, wsb = _wino_ws(B, H, W, dext, OD, Cin, Cout, x.device, dedicated=True)
-                        ws, wsb, v_ready = _shared_wino_ws(ctx.wshare, "bwd", ws, wsb, (w.data_ptr(), Cin, Cout, ty))
-                    rec = ctx.fuse_in
-                    if (rec is not None and rec.armed and (Cin % 256 == 0 or 256 % Cin == 0)
-                            and not _per_item(B, H * W * max(D, OD), max(Cin, Cout), 0, 0)
-                            and _fuse_final(ctx.link, x, acc)):
-                        dres_f = torch.empty_like(x) if rec.need_res else None
-                        bws, bwsb = _bn_fuse_ws(rec, B, H, W, D, Cin, x.device)
-                        d = rec.descriptor(dres_f)
-                        if vd is not None:
-                            check(L.m3d_conv3d_bwd_data_wino_xv(ptr(dz), ptr(w), B, H, W, D, Cin, Cout, OD,
-                                                                geo.pad[2], ptr(dx), acc, ptr(ws), wsb, ptr(vd[0]), ty,
-                                                                ctypes.addressof(d), ptr(bws), bwsb, stream()),
-                                  "conv3d_bwd_data_wino_xv(bn)")
-                        else:
-                            check(L.m3d_conv3d_bwd_data_wino_bny(ptr(dz), ptr(w), B, H, W, D, Cin, Cout, OD,
-                                                                 geo.pad[2], ptr(dx), acc, ptr(ws), wsb, v_ready,
-                                                                 ctypes.addressof(d), ptr(bws), bwsb, ty, stream()),
-                                  "conv3d_bwd_data_wino_bn")
-                        rec.buf, rec.dres, rec.done = dx, dres_f, True
-                        fused_nel = x.numel() * (1 + (rec.z is not None) + rec.need_res)
-                    elif vd is not None:
-                        check(L.m3d_conv3d_bwd_data_wino_xv(ptr(dz), ptr(w), B, H, W, D, Cin, Cout, OD, geo.pad[2],
-                                                            ptr(dx), acc, ptr(ws), wsb, ptr(vd[0]), ty, None, None, 0,
-                                                            stream()), "conv3d_bwd_data_wino_xv")
-                    else:
-                        check(L.m3d_conv3d_bwd_data_wino_vy(ptr(dz), ptr(w), B, H, W, D, Cin, Cout, OD,
-                                                            geo.pad[2], ptr(dx), acc, ptr(ws), wsb, v_ready, ty,
-                                                            stream()), "conv3d_bwd_data_wino")
-                    _shared_wino_release(ctx.wshare)
-                if logging:
-                    _log("wino_dgrad", direct, _wino_exec(B, OH, OW, OD, Cin, Cout, int(L.m3d_conv3d_wino_dgrad_tile_z()),
-                                                          ty or int(L.m3d_conv3d_wino_dgrad_tile_y())),
-                         4.0 * (dz.numel() + w.numel() + x.numel() * (1 + acc) + fused_nel), "bwd_data", ctx.name,
-                         td, "x3")
-                dx = _link_park(ctx.link, dx, acc)
-            if has_w and WGRAD_LAST:
-                wgrad()
-            _grad_done(grads, side)
-            ctx.halo = None
-            ctx.fuse_in = None
-            return (dx, (dres if need_res else None), None, None, None, None, None, None, None, None, None, None,
-                    None, None, None, None)
-        if halo is not None and ctx.need_dx:
+            if halo is not None:
+                halo[0].record_stream(side)
+        if halo is not None and not ctx.wino and ctx.need_dx:
             raise ValueError("the stem's halo form has no data gradient (its input is the volume)")
-        strided_x3 = (WGRAD1_STRIDED_X3 and halo is None and geo.k == (1, 1, 1) and geo.stride == (2, 2, 1)
-                      and geo.pad == (0, 0, 0) and (OH, OW, OD) == ((H + 1) // 2, (W + 1) // 2, D)
-                      and Cin % 4 == 0 and Cout >= 65)      # (_wgrad1_x3 of the stride-1 form)
-
-        def wgrad_d():
-            with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
-                tw = _span()
-                if halo is not None:        # the stem on a depth slab: halo planes beside the slab
-                    check(L.m3d_conv3d_bwd_weight_halo(ptr(x), ptr(halo[0]), halo[1], halo[2], halo[0].shape[3] // 2,
-                                                       ptr(dz), B, H, W, D, Cin, kh, kw, kd, Cout, OH, OW, OD,
-                                                       *geo.stride, *geo.pad, ptr(grads["kernel"]), stream()),
-                          "conv3d_bwd_weight_halo")
-                elif strided_x3:
-                    # the stage-first blocks' (2,2,1)-strided 1x1x1 convs: their input rows
-                    # gathered once (x[:, ::2, ::2]), then the stride-1 split-GEMM gradient
-                    xs = torch.empty((B, OH, OW, OD, Cin), device=x.device, dtype=torch.float32)
-                    check(L.m3d_subsample221_fwd(ptr(x), B, H, W, D, Cin, ptr(xs), stream()), "subsample221")
-                    check(L.m3d_conv3d_bwd_weight(ptr(xs), ptr(dz), B, OH, OW, OD, Cin, 1, 1, 1, Cout, OH, OW, OD,
-                                                  1, 1, 1, 0, 0, 0, ptr(grads["kernel"]), stream()),
-                          "conv3d_bwd_weight")
-                    del xs
-                else:
-                    check(L.m3d_conv3d_bwd_weight(ptr(x), ptr(dz), B, H, W, D, Cin, kh, kw, kd, Cout, OH,
-                                                  OW, OD, *geo.stride, *geo.pad, ptr(grads["kernel"]),
-                                                  stream()), "conv3d_bwd_weight")
-                if logging:
-                    _log(f"conv{kh}_wgrad", direct, direct, 4.0 * (x.numel() + dz.numel() + w.numel()),
-                         "bwd_weight", ctx.name, tw,
-                         "x3" if halo is None and (strided_x3 or _wgrad1_x3(geo, Cin, Cout, (H, W, D))) else "f32")
-        has_w = grads.get("kernel") is not None
-        if has_w and not WGRAD_LAST:
-            wgrad_d()
-        dx = None
-        link = ctx.link
-        acc = 0
-        td = _span()
-        rec = ctx.fuse_in
-        fused_nel = 0
-        if ctx.need_dx:
-            strided = any(s != 1 for s in geo.stride)
-            dx, acc = _link_take(link, x)                     # dx = parked gradient + conv^T dz
-            if dx is None:
-                dx = (torch.zeros if strided else torch.empty)(x.shape, device=x.device, dtype=torch.float32)
-            wd, dzd, cpad = w, dz, Cout
-            if Cout % 32:   # bwd-data stages 32-channel slices of dz: zero-pad the channel dim
-                cpad = -(-Cout // 32) * 32
-                wd = torch.zeros((kh, kw, kd, Cin, cpad), device=w.device, dtype=torch.float32)
-                wd[..., :Cout] = w
-                dzd = torch.zeros((B, OH, OW, OD, cpad), device=dz.device, dtype=torch.float32)
-                dzd[..., :Cout] = dz
-            nsk = _splitk(x.shape, geo, Cin, cpad, 1)
-            dx_x3 = cpad == Cout and not acc and _conv1_x3(x.shape, geo, Cout, Cin, bwd_data=True)
-            dx_x3f = (cpad == Cout and X3_BN_FUSE and rec is not None and rec.armed and (X3_BN_FUSE_ACC or not acc)
-                      and _conv1_x3(x.shape, geo, Cout, Cin, bwd_data=True, fused=True))
-            if dx_x3f and _fuse_final(link, x, acc):
-                # the producer's BN-ReLU backward in the split GEMM's epilogue (+ the parked gradient)
-                dx_x3 = True
-                planes = ctx.x3_bwd if ctx.x3_bwd is not None else _x3_planes(w, Cin, Cout, False)
-                dres_f = torch.empty_like(x) if rec.need_res else None
-                bws, bwsb = _bn_fuse_ws(rec, B, H, W, D, Cin, x.device)
-                d = rec.descriptor(dres_f)
-                check(L.m3d_conv3d_bwd_data_x3_bna(ptr(dz), ptr(planes), B, H, W, D, Cin, Cout, ptr(dx), acc,
-                                                   ctypes.addressof(d), ptr(bws), bwsb, stream()),
-                      "conv3d_bwd_data_x3_bna")
-                rec.buf, rec.dres, rec.done = dx, dres_f, True
-                fused_nel = x.numel() * (1 + (rec.z is not None) + rec.need_res)
-            elif dx_x3:
-                planes = ctx.x3_bwd if ctx.x3_bwd is not None else _x3_planes(w, Cin, Cout, False)
-                check(L.m3d_conv3d_bwd_data_x3(ptr(dz), ptr(planes), B, H, W, D, Cin, Cout, ptr(dx), stream()),
-                      "conv3d_bwd_data_x3")
-            elif (nsk > 1 and rec is not None and rec.armed and not strided and (OH, OW, OD) == (H, W, D)
-                  and not _per_item(B, H * W * D, Cin, OH * OW * OD, cpad) and _fuse_final(link, x, acc)):
-                wsk = torch.empty((nsk, M * Cin), device=x.device, dtype=torch.float32)
-                dres_f = torch.empty_like(x) if rec.need_res else None
-                bws, bwsb = _bn_fuse_ws(rec, B, H, W, D, Cin, x.device)
-                d = rec.descriptor(dres_f)
-                check(L.m3d_conv3d_bwd_data_splitk_bn(ptr(dzd), ptr(wd), B, H, W, D, Cin, cpad, ptr(dx), acc, nsk,
-                                                      ptr(wsk), wsk.numel() * 4, ctypes.addressof(d), ptr(bws),
-                                                      bwsb, stream()), "conv3d_bwd_data_splitk_bn")
-                rec.buf, rec.dres, rec.done = dx, dres_f, True
-                fused_nel = x.numel() * (1 + (rec.z is not None) + rec.need_res)
-            elif nsk > 1:
-                wsk = torch.empty((nsk, M * Cin), device=x.device, dtype=torch.float32)
-                check(L.m3d_conv3d_bwd_data_splitk(ptr(dzd), ptr(wd), B, H, W, D, Cin, cpad, OH, OW, OD,
-                                                   *geo.stride, ptr(dx), acc, nsk, ptr(wsk), wsk.numel() * 4,
-                                                   stream()), "conv3d_bwd_data_splitk")
-            elif (rec is not None and rec.armed and not strided and (OH, OW, OD) == (H, W, D)
-                  and not _per_item(B, H * W * D, Cin, OH * OW * OD, cpad) and _fuse_final(link, x, acc)):
-                dres_f = torch.empty_like(x) if rec.need_res else None
-                bws, bwsb = _bn_fuse_ws(rec, B, H, W, D, Cin, x.device)
-                d = rec.descriptor(dres_f)
-                check(L.m3d_conv3d_bwd_data_bn(ptr(dzd), ptr(wd), B, H, W, D, Cin, kh, kw, kd, cpad, OH, OW, OD,
-                                               *geo.stride, *geo.pad, ptr(dx), acc, ctypes.addressof(d), ptr(bws),
-                                               bwsb, stream()), "conv3d_bwd_data_bn")
-                rec.buf, rec.dres, rec.done = dx, dres_f, True
-                fused_nel = x.numel() * (1 + (rec.z is not None) + rec.need_res)
-            else:
-                check(L.m3d_conv3d_bwd_data(ptr(dzd), ptr(wd), B, H, W, D, Cin, kh, kw, kd, cpad, OH, OW,
-                                            OD, *geo.stride, *geo.pad, ptr(dx), acc, stream()),
-                      "conv3d_bwd_data")
-            if logging:
-                _log(f"conv{kh}_dgrad", direct, direct,
-                     4.0 * (dz.numel() + w.numel() + x.numel() * (1 + acc) + fused_nel),
-                     "bwd_data", ctx.name, td, "x3" if dx_x3 else "f32")
-            dx = _link_park(link, dx, acc)
-        if has_w and WGRAD_LAST:
-            wgrad_d()
+        wgrad, dgrad = (_wino_wgrad, _wino_dgrad) if ctx.wino else (_direct_wgrad, _direct_dgrad)
+        # data gradient first: a HIP-graph replay keeps the compute path on its own queue (WGRAD_LAST)
+        if dw is not None and not WGRAD_LAST:
+            wgrad(ctx, x, dz, w, dw, side, direct)
+        dx = dgrad(ctx, x, dz, w, direct) if ctx.need_dx else None
+        if dw is not None and WGRAD_LAST:
+            wgrad(ctx, x, dz, w, dw, side, direct)
         _grad_done(grads, side)
-        dr = None
-        if need_res:
-            if ctx.res_mode == 1 and link is not None and link.mode == "res" and not trivial:
-                link.buf = dres                               # consumed by the input conv's backward
-            elif ctx.res_mode == 1:
-                dr = dres
-            else:
-                rb, rh, rw, rd, rc = ctx.res_shape
-                tu = _span()
-                dr = torch.empty(ctx.res_shape, device=dy.device, dtype=torch.float32)
-                check(L.m3d_upsample221_bwd(ptr(dres), rb, rh, rw, rd, rc, ptr(dr), 0, stream()),
-                      "upsample221_bwd")
-                _log("upsample_bwd", 0, 0, 4.0 * (dres.numel() + dr.numel()), "bwd_data", ctx.name, tu)
-        ctx.fuse_in = None
-        return dx, dr, None, None, None, None, None, None, None, None, None, None, None, None, None, None
+        ctx.halo = ctx.fuse_in = None
+        return (dx, _residual_grad(ctx, dres)) + (None,) * 14
 
 
 def _stem_halo(geo, cin, cout, res_mode):
@@ -1547,7 +1546,7 @@ RPN_OUT_SIDE = True
 
 
 def _rpn_out_wgrad(L, side, xb, dz, H, W, D, Cin, npad, grads):
-    with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
+    with _on_side(side):
         check(L.m3d_conv3d_bwd_weight(ptr(xb), ptr(dz), 1, H, W, D, Cin, 1, 1, 1, npad, H,
                                       W, D, 1, 1, 1, 0, 0, 0, ptr(grads["kernel"]),
                                       stream()), "rpn_out_wgrad")
@@ -1630,8 +1629,7 @@ class _RPNOut(torch.autograd.Function):
                 (0, npad - n_out))
             if grads.get("bias") is not None:
                 # all levels' rows at once (one column sum of the level-concatenated matrix)
-                bias_grad(dz_all, R, npad, grads["bias"], grads,
-                          ctx.bias_batch if "rpn" in BIAS_BATCH_UNITS.split("+") else None)
+                bias_grad(dz_all, R, npad, grads["bias"], grads, ctx.bias_batch)
             off = 0
             for li, (s, r) in enumerate(zip(shared, rows)):
                 xb = s[b:b + 1]
