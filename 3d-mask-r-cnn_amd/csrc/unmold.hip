@@ -21,6 +21,13 @@
 //                          zeroed, IoU = inter / (area_pred + area_gt - inter)
 //   K4 um_paste_kernel     the same traversal writing 1 into dense / seg_union
 //   K5 um_areas_kernel     column counts of the [V,G] GT bytes
+//   K6 um_label_of_kernel  numbers the listed rows (one workgroup, a scan);
+//      um_labels_kernel    K4's traversal, a 32-bit atomic max of the row's
+//                          label per set voxel -> the instance label volume
+//   K7 um_pixelwise_kernel one streaming pass over labels + GT bytes -> tp /
+//                          fp / fn of "any instance" against "any GT mask"
+//   K8 um_stack_kernel     labels [H,W,D] int32 -> the TIFF page order [D,H,W]
+//                          uint8 / uint16, a tiled transpose through LDS
 // All scalar arithmetic is fp64 on the fp32 inputs in the order of
 // tests/unmoldref.py (no contraction: the Makefile's -ffp-contract=off), so the
 // thresholds and every integer output equal that restatement bit for bit.  The
@@ -544,6 +551,186 @@ __global__ __launch_bounds__(UM_BLOCK) void um_areas_kernel(const uint8_t* __res
     }
 }
 
+// ---- instance labels, pixelwise counts, the TIFF page order --------------------
+constexpr int UM_SCAN_BLOCK = 1024;      // one workgroup numbers the rows: 64 rows per lane at 65535
+constexpr int UM_MAX_LABEL = 65535;      // a label fits the widest sample m3d_labels_stack writes
+constexpr int UM_PX_UNROLL = 8;          // voxels per (voxel, group) lane between two barriers
+constexpr int UM_TR_TILE = 64;           // the [W,D] -> [D,W] transpose tile (64 x 64 labels in LDS)
+
+// label_of[row] = 1 + the row's index among the listed rows (status != NOT_KEPT
+// and keep[row] != 0), 0 for the others: an exclusive scan in one workgroup.
+__global__ __launch_bounds__(UM_SCAN_BLOCK) void um_label_of_kernel(const int32_t* __restrict__ status,
+                                                                    const uint8_t* __restrict__ keep, int n,
+                                                                    int32_t* __restrict__ label_of) {
+    __shared__ int ws[UM_SCAN_BLOCK / 64];
+    const int t = threadIdx.x;
+    const int per = (n + UM_SCAN_BLOCK - 1) / UM_SCAN_BLOCK;
+    const int lo = t * per < n ? t * per : n, hi = lo + per < n ? lo + per : n;
+    int c = 0;
+    for (int i = lo; i < hi; ++i) c += status[i] != M3D_UNMOLD_NOT_KEPT && (keep == nullptr || keep[i] != 0);
+    int v = c;                                                  // inclusive scan of the wave
+    for (int o = 1; o < 64; o <<= 1) {
+        const int x = __shfl_up(v, o);
+        if ((t & 63) >= o) v += x;
+    }
+    if ((t & 63) == 63) ws[t >> 6] = v;
+    __syncthreads();
+    int run = v - c;
+    for (int w = 0; w < (t >> 6); ++w) run += ws[w];
+    for (int i = lo; i < hi; ++i) {
+        const bool listed = status[i] != M3D_UNMOLD_NOT_KEPT && (keep == nullptr || keep[i] != 0);
+        label_of[i] = listed ? ++run : 0;
+    }
+}
+
+// um_paste_kernel's traversal; a set voxel takes the largest label of the
+// detections set there (the reference paints in ascending order: the later
+// detection wins).  The maximum does not depend on the order of arrival.
+__global__ __launch_bounds__(UM_BLOCK) void um_labels_kernel(
+        const uint8_t* __restrict__ small, const int32_t* __restrict__ box_i, const int32_t* __restrict__ status,
+        const double* __restrict__ stats, const int32_t* __restrict__ label_of, int m, int H, int W, int D,
+        int slabs, int32_t* __restrict__ labels) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t um_sm[];
+    const int t = threadIdx.x;
+    const int64_t nd = blockIdx.x / (unsigned)slabs;
+    const int sl = (int)(blockIdx.x % (unsigned)slabs);
+    const int lab = label_of[nd];
+    if (lab <= 0 || status[nd] != M3D_UNMOLD_OK) return;        // unlisted, or listed without a mask
+    const UmBox bx = um_box(box_i, nd, H, W, D);
+    const int nchunks = (bx.nvox + UM_BLOCK - 1) / UM_BLOCK;
+    if (sl >= nchunks) return;
+    const int n = m * m * m;
+    um_stage(um_sm, small + nd * n, n);
+    __syncthreads();
+    const double ry = (double)m / (double)bx.hh, rx = (double)m / (double)bx.ww, rz = (double)m / (double)bx.dd;
+    const double rthr = stats[nd * 8 + 7];
+    for (int c = sl; c < nchunks; c += slabs) {
+        const int q = c * UM_BLOCK + t;
+        if (q >= bx.nvox) continue;
+        const int oz = q % bx.dd, r = q / bx.dd;
+        const int ox = r % bx.ww, oy = r / bx.ww;
+        if (!um_set(um_sm, m, ry, rx, rz, oy, ox, oz, rthr)) continue;
+        const int64_t lin = ((int64_t)(bx.y1 + oy) * W + (bx.x1 + ox)) * D + (bx.z1 + oz);
+        atomicMax(&labels[lin], lab);
+    }
+}
+
+// counts[0..2] += tp, fp, fn of (labels > 0) against (any GT byte of the voxel
+// set).  Lanes are (voxel, 4-byte group) as in um_areas_kernel; a lane whose
+// groups hold a set byte raises its voxel's flag in LDS, then one lane per
+// voxel takes the label and the flag.  A tile is UM_PX_UNROLL sweeps of the
+// workgroup, all its loads in flight at once.  G == 0: no GT byte is read.
+__global__ __launch_bounds__(UM_BLOCK) void um_pixelwise_kernel(const int32_t* __restrict__ labels,
+                                                                const uint8_t* __restrict__ gt, int64_t V, int G,
+                                                                unsigned long long* __restrict__ counts) {
+    __shared__ int flags[2 * UM_BLOCK * UM_PX_UNROLL];          // two tiles of voxel flags, used in turn
+    __shared__ int part[3][UM_BLOCK / 64];
+    const int t = threadIdx.x;
+    const int ng = (G + 3) / 4;                                 // 4-byte groups of a voxel's GT row
+    const int gpv = ng < 1 ? 1 : (ng < UM_BLOCK ? ng : UM_BLOCK);   // lanes per voxel
+    const int vpi = UM_BLOCK / gpv;                             // voxels per sweep of the workgroup
+    const int T = vpi * UM_PX_UNROLL;                           // voxels per tile
+    const int j = t % gpv, slot0 = t / gpv;
+    // 4 <= G <= 1024: a lane has one group and loads it as one dword; the lane
+    // of the row's tail group takes the row's last four bytes instead (they
+    // overlap the group before it, which an "any" does not mind): no lane reads
+    // past its row and none loops over bytes.
+    const bool one = ng <= UM_BLOCK && G >= 4;
+    const int off = j * 4 < G - 4 ? j * 4 : G - 4;
+    int tp = 0, fp = 0, fn = 0;
+    for (int i = t; i < 2 * UM_BLOCK * UM_PX_UNROLL; i += UM_BLOCK) flags[i] = 0;
+    __syncthreads();
+    int buf = 0;
+    for (int64_t base = (int64_t)blockIdx.x * T; base < V; base += (int64_t)gridDim.x * T, buf ^= 1) {
+        int* fl = flags + buf * (UM_BLOCK * UM_PX_UNROLL);
+        int lab[UM_PX_UNROLL];                                  // the tile's labels, in flight with the GT loads
+#pragma unroll
+        for (int k = 0; k < UM_PX_UNROLL; ++k) {
+            const int i = t + k * UM_BLOCK;
+            lab[k] = (i < T && base + i < V) ? labels[base + i] : 0;
+        }
+        if (slot0 < vpi && one) {
+            uint32_t w[UM_PX_UNROLL];
+#pragma unroll
+            for (int u = 0; u < UM_PX_UNROLL; ++u) {            // every load of the tile goes out before the first use
+                const int64_t v = base + u * vpi + slot0;
+                w[u] = 0;
+                if (v < V) __builtin_memcpy(&w[u], gt + v * G + off, 4);        // 64-bit byte offset
+            }
+#pragma unroll
+            for (int u = 0; u < UM_PX_UNROLL; ++u)
+                if (w[u]) fl[u * vpi + slot0] = 1;              // LDS; every writer of a flag writes 1
+        } else if (slot0 < vpi) {                               // G > 1024: a lane walks its groups; G < 4: byte loads
+            for (int u = 0; u < UM_PX_UNROLL; ++u) {
+                const int64_t v = base + u * vpi + slot0;
+                if (v >= V) break;
+                const uint8_t* __restrict__ row = gt + v * G;
+                bool any = false;
+                for (int g = j; g < ng; g += gpv) {
+                    if (g * 4 + 4 <= G) {
+                        uint32_t w;
+                        __builtin_memcpy(&w, row + g * 4, 4);
+                        any |= w != 0;
+                    } else {                                    // the row's tail group: never read past it
+                        for (int b = g * 4; b < G; ++b) any |= row[b] != 0;
+                    }
+                }
+                if (any) fl[u * vpi + slot0] = 1;
+            }
+        }
+        // One barrier per tile: the next tile raises flags in the other half, and
+        // the one after it passes the next barrier first, behind every reader here.
+        lds_barrier();
+#pragma unroll
+        for (int k = 0; k < UM_PX_UNROLL; ++k) {
+            const int i = t + k * UM_BLOCK;
+            if (i < T && base + i < V) {
+                const bool p = lab[k] > 0, g = fl[i] != 0;
+                fl[i] = 0;
+                tp += p && g;
+                fp += p && !g;
+                fn += !p && g;
+            }
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        tp += __shfl_xor(tp, o);
+        fp += __shfl_xor(fp, o);
+        fn += __shfl_xor(fn, o);
+    }
+    if ((t & 63) == 0) {
+        part[0][t >> 6] = tp;
+        part[1][t >> 6] = fp;
+        part[2][t >> 6] = fn;
+    }
+    __syncthreads();
+    if (t < 3) {
+        unsigned long long sum = 0;                             // a workgroup sees fewer than 2^31 voxels
+        for (int w = 0; w < UM_BLOCK / 64; ++w) sum += (unsigned long long)part[t][w];
+        if (sum) atomicAdd(&counts[t], sum);
+    }
+}
+
+// stack[d,h,w] = (T)labels[h,w,d]: each h plane's [W,D] -> [D,W] through a
+// padded LDS tile, reads contiguous along D, writes contiguous along W.
+template <typename T>
+__global__ __launch_bounds__(UM_BLOCK) void um_stack_kernel(const int32_t* __restrict__ labels, int H, int W, int D,
+                                                            int tw, int td, T* __restrict__ stack) {
+    __shared__ int32_t tile[UM_TR_TILE][UM_TR_TILE + 1];        // [w][d], padded: no bank conflict either way
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const unsigned b = blockIdx.x;
+    const int d0 = (int)(b % (unsigned)td) * UM_TR_TILE;
+    const int w0 = (int)((b / (unsigned)td) % (unsigned)tw) * UM_TR_TILE;
+    const int h = (int)(b / ((unsigned)td * (unsigned)tw));
+    if (d0 + tx < D)
+        for (int r = ty; r < UM_TR_TILE && w0 + r < W; r += UM_BLOCK / 64)
+            tile[r][tx] = labels[((int64_t)h * W + (w0 + r)) * D + (d0 + tx)];
+    __syncthreads();
+    if (w0 + tx < W)
+        for (int r = ty; r < UM_TR_TILE && d0 + r < D; r += UM_BLOCK / 64)
+            stack[((int64_t)(d0 + r) * H + h) * W + (w0 + tx)] = (T)tile[tx][r];
+}
+
 static int um_slabs(int64_t vol) {
     int64_t s = (vol + UM_SLAB_VOX - 1) / UM_SLAB_VOX;
     return (int)(s < 1 ? 1 : (s > UM_MAX_SLABS ? UM_MAX_SLABS : s));
@@ -644,4 +831,66 @@ extern "C" int m3d_mask_areas(const uint8_t* gt_masks, int64_t H, int64_t W, int
     hipLaunchKernelGGL(um_areas_kernel, dim3(grid_for(V, vpi * 8, 4096)), dim3(UM_BLOCK), 0, st(s), gt_masks, V,
                        (int)G, area_gt);
     return check_launch("um_areas_kernel");
+}
+
+extern "C" int m3d_unmold_labels(const uint8_t* small, const int32_t* box_i, const int32_t* status,
+                                 const double* stats, const uint8_t* keep, int64_t max_inst, int64_t m, int64_t H,
+                                 int64_t W, int64_t D, int32_t* label_of, int32_t* labels, m3d_stream_t s) {
+    if (int rc = um_check(max_inst, m, H, W, D)) return rc;
+    if (max_inst > UM_MAX_LABEL) return einval("unmold_labels: max_inst must be <= 65535 (a label fits 16 bits)");
+    if (small == nullptr || box_i == nullptr || status == nullptr || stats == nullptr || label_of == nullptr ||
+        labels == nullptr)
+        return einval("unmold_labels: NULL pointer");
+    if (hipMemsetAsync(labels, 0, sizeof(int32_t) * (size_t)(H * W * D), st(s)) != hipSuccess)
+        return check_launch("unmold_labels: memset");
+    if (max_inst == 0) return M3D_OK;
+    hipLaunchKernelGGL(um_label_of_kernel, dim3(1), dim3(UM_SCAN_BLOCK), 0, st(s), status, keep, (int)max_inst,
+                       label_of);
+    if (int rc = check_launch("um_label_of_kernel")) return rc;
+    const int slabs = um_slabs(H * W * D);
+    hipLaunchKernelGGL(um_labels_kernel, dim3((unsigned)(max_inst * slabs)), dim3(UM_BLOCK),
+                       (size_t)((m * m * m + 15) & ~(int64_t)15), st(s), small, box_i, status, stats, label_of,
+                       (int)m, (int)H, (int)W, (int)D, slabs, labels);
+    return check_launch("um_labels_kernel");
+}
+
+// shapes shared by the two label-volume entries: 0 = fine
+static int um_check_volume(const char* who, int64_t H, int64_t W, int64_t D) {
+    if (H <= 0 || W <= 0 || D <= 0) return (set_error("%s: H, W and D must be positive", who), M3D_EINVAL);
+    if (H > 0x7FFFFFFF / W || H * W > 0x7FFFFFFF / D)
+        return (set_error("%s: H * W * D must fit 31 bits", who), M3D_EINVAL);
+    return M3D_OK;
+}
+
+extern "C" int m3d_label_pixelwise(const int32_t* labels, const uint8_t* gt_masks, int64_t H, int64_t W, int64_t D,
+                                   int64_t G, int64_t* counts, m3d_stream_t s) {
+    if (int rc = um_check_volume("label_pixelwise", H, W, D)) return rc;
+    if (G < 0 || G > 0x7FFFFFFF) return einval("label_pixelwise: G must be in [0, 2^31)");
+    if (labels == nullptr || counts == nullptr) return einval("label_pixelwise: NULL pointer");
+    if (G > 0 && gt_masks == nullptr) return einval("label_pixelwise: gt_masks must not be NULL when G > 0");
+    if (hipMemsetAsync(counts, 0, sizeof(int64_t) * 3, st(s)) != hipSuccess)
+        return check_launch("label_pixelwise: memset");
+    const int64_t V = H * W * D;
+    const int64_t ng = (G + 3) / 4;
+    const int vpi = UM_BLOCK / (int)(ng < 1 ? 1 : (ng < UM_BLOCK ? ng : UM_BLOCK));
+    hipLaunchKernelGGL(um_pixelwise_kernel, dim3(grid_for(V, vpi * UM_PX_UNROLL, 4096)), dim3(UM_BLOCK), 0, st(s),
+                       labels, gt_masks, V, (int)G, reinterpret_cast<unsigned long long*>(counts));
+    return check_launch("um_pixelwise_kernel");
+}
+
+extern "C" int m3d_labels_stack(const int32_t* labels, int64_t H, int64_t W, int64_t D, int64_t bytes_per_sample,
+                                void* stack, m3d_stream_t s) {
+    if (int rc = um_check_volume("labels_stack", H, W, D)) return rc;
+    if (bytes_per_sample != 1 && bytes_per_sample != 2)
+        return einval("labels_stack: bytes_per_sample must be 1 or 2");
+    if (labels == nullptr || stack == nullptr) return einval("labels_stack: NULL pointer");
+    const int tw = (int)((W + UM_TR_TILE - 1) / UM_TR_TILE), td = (int)((D + UM_TR_TILE - 1) / UM_TR_TILE);
+    const dim3 grid((unsigned)(H * tw * td));                   // <= H * W * D < 2^31
+    if (bytes_per_sample == 1)
+        hipLaunchKernelGGL(um_stack_kernel<uint8_t>, grid, dim3(UM_BLOCK), 0, st(s), labels, (int)H, (int)W, (int)D,
+                           tw, td, static_cast<uint8_t*>(stack));
+    else
+        hipLaunchKernelGGL(um_stack_kernel<uint16_t>, grid, dim3(UM_BLOCK), 0, st(s), labels, (int)H, (int)W,
+                           (int)D, tw, td, static_cast<uint16_t*>(stack));
+    return check_launch("um_stack_kernel");
 }

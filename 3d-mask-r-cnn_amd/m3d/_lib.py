@@ -188,6 +188,9 @@ _SIGS = {
     "m3d_unmold_finalize": [c_p, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p],
     "m3d_unmold_paste": [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p],
     "m3d_mask_areas": [c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p],
+    "m3d_unmold_labels": [c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p],
+    "m3d_label_pixelwise": [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p],
+    "m3d_labels_stack": [c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p],
     "m3d_maxpool3d_fwd": [c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32,
                           c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, c_p, c_p, c_p],
     "m3d_maxpool3d_bwd": [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32,

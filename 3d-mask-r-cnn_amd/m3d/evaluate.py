@@ -10,7 +10,13 @@ volume; ``mask_overlaps`` scores them against ground-truth masks [H,W,D,G]
 over each detection's box voxels counts the intersections as integers.
 ``compute_matches`` / ``compute_ap`` are the reference's greedy matching and
 VOC-style AP in numpy on the [N,G] IoU matrix -- the end of the pipeline, after
-one copy to the host.  GPU only: there is no CPU fallback.
+one copy to the host.  With ``labels=True`` the chain also builds the
+segmentation volume of instance labels on the device (``Unmolded.labels``,
+``label_stack`` for the TIFF page order), its pixelwise tp / fp / fn against
+the ground truth (``pixelwise_counts``), and the reference's pixelwise,
+instance-Dice and mask-level detection metrics (core/models.py:6153-6282,
+6644-6721) on the host from the integer counts.  GPU only: there is no CPU
+fallback.
 """
 from __future__ import annotations
 
@@ -35,6 +41,8 @@ class Unmolded:
       area_pred [max_inst] int32        set voxels of each instance mask
       dense     [max_inst,H,W,D] uint8  (dense=True)   masks = its [H,W,D,max_inst] view
       seg_union [H,W,D] uint8           (union=True)
+      labels    [H,W,D] int32           (labels=True)  the instance label volume
+      label_of  [max_inst] int32        (labels=True)  each row's label, 0 = not listed
 
     A detection whose status is not OK has an all-zero mask, as in the reference."""
 
@@ -43,6 +51,7 @@ class Unmolded:
         self.small, self.box_i, self.status, self.stats, self.area_pred = small, box_i, status, stats, area_pred
         self.dense, self.seg_union = dense, seg_union
         self.overlaps = None        # (iou, inter, area_pred, area_gt) when unmold_detections got gt_masks
+        self.labels = self.label_of = None
 
     @property
     def masks(self):
@@ -57,21 +66,38 @@ class Unmolded:
         passed: the sigmoid branch is not built)."""
         return self._to_host()
 
-    def _to_host(self, iou=None, inter=None, area_gt=None, gt_ids=None):
+    def label_stack(self):
+        """The label volume in TIFF page order: device tensor [D,H,W], uint8 when
+        max_inst <= 255 (every label fits), else uint16 -- chosen from the
+        shape, so nothing synchronises."""
+        if self.labels is None:
+            raise ValueError("label_stack needs unmold_detections(..., labels=True)")
+        H, W, D = self.image_shape
+        wide = int(self.status.shape[0]) > 255
+        out = torch.empty((D, H, W), device=self.labels.device, dtype=torch.uint16 if wide else torch.uint8)
+        _lib.check(_lib.load().m3d_labels_stack(_lib.ptr(self.labels), H, W, D, 2 if wide else 1, _lib.ptr(out),
+                                                _lib.stream()), "m3d_labels_stack")
+        return out
+
+    def _to_host(self, iou=None, inter=None, area_gt=None, gt_ids=None, label_of=None):
         """compact(), with the [max_inst,G] overlaps, area_gt [G] and device-side
         GT class ids [G] riding the same single copy (one int32 matrix: a row
-        per detection, one more for the two per-GT vectors)."""
+        per detection, one more for the two per-GT vectors).  With ``label_of``
+        [max_inst] (one more column of that copy) the list is the listed rows
+        (label_of > 0: the keep filter applied) and ``label_of`` is returned."""
         n = self.detections.shape[0]
         cols = [self.detections.view(torch.int32), self.status[:, None], self.area_pred[:, None]]
         G = 0 if inter is None else int(inter.shape[1])
         if G:
             cols += [inter, iou.view(torch.int32)]
+        if label_of is not None:
+            cols.append(label_of[:, None])
         packed = torch.cat(cols, 1)
         if G:
             last = torch.zeros((1, packed.shape[1]), dtype=torch.int32, device=packed.device)
             last[0, 10:10 + G] = area_gt
             if gt_ids is not None:
-                last[0, 10 + G:] = gt_ids.to(torch.int32)
+                last[0, 10 + G:10 + 2 * G] = gt_ids.to(torch.int32)
             packed = torch.cat([packed, last], 0)
         host = packed.cpu().numpy()
         det = host[:n, :8].copy().view(np.float32).reshape(n, 8)
@@ -79,16 +105,18 @@ class Unmolded:
         if (status == RANGE).any():
             raise ValueError("unmold_detections: mrcnn_mask holds values outside [-0.1, 1.1] (logits?) in rows "
                              f"{np.flatnonzero(status == RANGE).tolist()}; pass probabilities")
-        rows = np.flatnonzero(status != NOT_KEPT)
+        rows = np.flatnonzero(status != NOT_KEPT if label_of is None else host[:n, -1] > 0)
         H, W, D = self.image_shape
         boxes = det[rows, :6] * np.array([H, W, D, H, W, D], np.float32)
         out = {"boxes": boxes, "scores": det[rows, 7], "class_ids": det[rows, 6].astype(np.int32), "rows": rows,
                "status": status[rows].copy(), "area": area[rows].copy()}
         if G:
             out["inter"] = host[:n, 10:10 + G][rows].copy()
-            out["iou"] = host[:n, 10 + G:].copy().view(np.float32).reshape(n, G)[rows]
+            out["iou"] = host[:n, 10 + G:10 + 2 * G].copy().view(np.float32).reshape(n, G)[rows]
             out["area_gt"] = host[n, 10:10 + G].copy()
-            out["gt_ids"] = host[n, 10 + G:].copy()
+            out["gt_ids"] = host[n, 10 + G:10 + 2 * G].copy()
+        if label_of is not None:
+            out["label_of"] = host[:n, -1].copy()
         return out
 
 
@@ -142,12 +170,25 @@ def _count(u, gt):
     return iou, inter, area, area_gt
 
 
-def unmold_detections(detections, mrcnn_mask, image_shape, dense=False, union=False, gt_masks=None):
+def _keep_u8(keep, n):
+    ops._dev(keep)
+    if keep.dtype not in (torch.bool, torch.uint8) or tuple(keep.shape) != (n,):
+        raise ValueError(f"keep must be a bool / uint8 tensor [{n}], got {keep.dtype} {tuple(keep.shape)}")
+    keep = keep.contiguous()
+    return keep.view(torch.uint8) if keep.dtype == torch.bool else keep
+
+
+def unmold_detections(detections, mrcnn_mask, image_shape, dense=False, union=False, gt_masks=None, labels=False,
+                      keep=None):
     """detections [max_inst,8], mrcnn_mask [max_inst,m,m,m,C] probabilities of
     one image (a leading batch axis of 1 is accepted) -> Unmolded.  With
     ``gt_masks`` [H,W,D,G] the overlaps are counted in the same traversal of
-    the boxes and left in ``.overlaps`` (what mask_overlaps returns).  Nothing
-    synchronises."""
+    the boxes and left in ``.overlaps`` (what mask_overlaps returns).  With
+    ``labels`` the instance label volume ``.labels`` [H,W,D] int32 and the
+    rows' labels ``.label_of`` are built (the reference's seg[full > 0.5] = j
+    + 1 over its kept list, core/models.py:7023-7069); ``keep`` (bool / uint8
+    device tensor [max_inst]) drops rows from that list -- the caller's
+    confidence / size / NMS filters.  Nothing synchronises."""
     ops._dev(detections, mrcnn_mask)
     if detections.dim() == 3 and detections.shape[0] == 1:
         detections = detections[0]
@@ -156,6 +197,10 @@ def unmold_detections(detections, mrcnn_mask, image_shape, dense=False, union=Fa
     if detections.dim() != 2 or detections.shape[1] != 8:
         raise ValueError(f"detections must be [max_inst,8], got {tuple(detections.shape)}")
     n = int(detections.shape[0])
+    if keep is not None:
+        if not labels:
+            raise ValueError("keep filters the label list: pass labels=True")
+        keep = _keep_u8(keep, n)
     if mrcnn_mask.dim() != 5 or mrcnn_mask.shape[0] != n or len(set(mrcnn_mask.shape[1:4])) != 1:
         raise ValueError(f"mrcnn_mask must be [max_inst,m,m,m,C], got {tuple(mrcnn_mask.shape)}")
     m, C = int(mrcnn_mask.shape[1]), int(mrcnn_mask.shape[4])
@@ -182,7 +227,28 @@ def unmold_detections(detections, mrcnn_mask, image_shape, dense=False, union=Fa
     if dense or union:
         _lib.check(L.m3d_unmold_paste(p(small), p(box_i), p(status), p(stats), n, m, H, W, D, p(u.dense),
                                       p(u.seg_union), s), "m3d_unmold_paste")
+    if labels:
+        u.label_of = torch.empty(n, device=dev, dtype=torch.int32)
+        u.labels = torch.empty((H, W, D), device=dev, dtype=torch.int32)
+        _lib.check(L.m3d_unmold_labels(p(small), p(box_i), p(status), p(stats), p(keep), n, m, H, W, D,
+                                       p(u.label_of), p(u.labels), s), "m3d_unmold_labels")
     return u
+
+
+def pixelwise_counts(labels, gt_masks):
+    """labels [H,W,D] int32, gt_masks [H,W,D,G] (uint8 / bool, set = non-zero; G
+    may be 0) -> device int64 [3]: tp, fp, fn of (labels > 0) against (any GT
+    mask set), one streaming pass.  Nothing synchronises."""
+    ops._dev(labels)
+    if labels.dim() != 3 or labels.dtype != torch.int32:
+        raise ValueError(f"labels must be int32 [H,W,D], got {labels.dtype} {tuple(labels.shape)}")
+    H, W, D = (int(v) for v in labels.shape)
+    gt = _check_gt(gt_masks, (H, W, D))
+    G = int(gt.shape[3])
+    out = torch.empty(3, device=labels.device, dtype=torch.int64)
+    _lib.check(_lib.load().m3d_label_pixelwise(_lib.ptr(labels.contiguous()), _lib.ptr(gt) if G else None, H, W, D,
+                                               G, _lib.ptr(out), _lib.stream()), "m3d_label_pixelwise")
+    return out
 
 
 def mask_areas(gt_masks):
@@ -283,22 +349,115 @@ def compute_ap(overlaps, pred_class_ids, gt_class_ids, iou_threshold=0.5):
     return mAP, precision, recall, matched
 
 
-def evaluate_detections(detections, mrcnn_mask, image_shape, gt_class_ids, gt_masks, iou_threshold=0.5):
+def pixelwise_metrics(tp, fp, fn):
+    """(precision, recall, f1, iou) of the reference's _pixelwise_metrics
+    (core/models.py:6153-6164) from its three int64 counts: float64, its 1e-9
+    terms and its zero-denominator branches."""
+    tp, fp, fn = np.int64(tp), np.int64(fp), np.int64(fn)
+    prec = (tp / (tp + fp + 1e-9)) if (tp + fp) > 0 else 0.0
+    rec = (tp / (tp + fn + 1e-9)) if (tp + fn) > 0 else 0.0
+    f1 = (2.0 * prec * rec / (prec + rec + 1e-9)) if (prec + rec) > 0 else 0.0
+    iou = (tp / (tp + fp + fn + 1e-9)) if (tp + fp + fn) > 0 else 0.0
+    return float(prec), float(rec), float(f1), float(iou)
+
+
+def _mask_iou(inter, area_pred, area_gt):
+    inter = np.asarray(inter).astype(np.int64)
+    p_sum, t_sum = np.asarray(area_pred).astype(np.int64), np.asarray(area_gt).astype(np.int64)
+    union = (p_sum[:, None] + t_sum[None, :]) - inter
+    return inter, p_sum, t_sum, inter / np.maximum(union, 1)
+
+
+def instance_dice(inter, area_pred, area_gt, iou_thr=0.5):
+    """The reference's _instance_dice (core/models.py:6166-6282) on the integer
+    counts inter [K,G], area_pred [K], area_gt [G] of the listed masks ->
+    (mean, std, n).  iou = inter / max(union, 1) in float64; repeatedly the
+    global argmax over the unused rows and columns, until it is under
+    ``iou_thr``; Dice = 2 inter / (P + T) of each pair; np.mean / np.std."""
+    inter, p_sum, t_sum, iou = _mask_iou(inter, area_pred, area_gt)
+    K, G = iou.shape
+    if K == 0 or G == 0:
+        return 0.0, 0.0, 0
+    used_p, used_g = np.zeros(K, bool), np.zeros(G, bool)
+    dices = []
+    while True:
+        masked = iou.copy()
+        masked[used_p, :] = -1.0
+        masked[:, used_g] = -1.0
+        k, g = np.unravel_index(np.argmax(masked), masked.shape)
+        if masked[k, g] < iou_thr:
+            break
+        denom = p_sum[k] + t_sum[g]
+        dices.append(float((2.0 * inter[k, g] / denom) if denom > 0 else 0.0))
+        used_p[k] = used_g[g] = True
+    if not dices:
+        return 0.0, 0.0, 0
+    return float(np.mean(dices)), float(np.std(dices)), len(dices)
+
+
+def detection_performance(inter, area_pred, area_gt, thr=0.5):
+    """The mask-level detection counts of the reference's _compute_mask_metrics
+    (core/models.py:6663-6706) on the same counts -> dict tp, fp, fn, recall,
+    precision: the best remaining pair is matched and its row and column are
+    zeroed, until the best IoU is under ``thr``.  Without predictions or
+    without ground truths (where the reference reports nothing) every
+    prediction is a fp and every ground truth a fn."""
+    _, _, _, iou = _mask_iou(inter, area_pred, area_gt)
+    K, G = iou.shape
+    matched_p, matched_g = np.zeros(K, bool), np.zeros(G, bool)
+    while K > 0 and G > 0:
+        i, j = np.unravel_index(np.argmax(iou), iou.shape)
+        if iou[i, j] < thr:
+            break
+        matched_p[i] = matched_g[j] = True
+        iou[i, :] = 0
+        iou[:, j] = 0
+    tp = np.sum(matched_p)
+    fp = K - tp
+    fn = G - np.sum(matched_g)
+    return {"tp": int(tp), "fp": int(fp), "fn": int(fn), "recall": float(tp / (tp + fn)) if (tp + fn) > 0 else 0.0,
+            "precision": float(tp / (tp + fp)) if (tp + fp) > 0 else 0.0}
+
+
+def write_detection_csv(path, class_ids, boxes):
+    """The reference's save_classes_and_boxes table (core/models.py:6313-6336):
+    header class,y1,x1,z1,y2,x2,z2, then one line per listed detection in label
+    order; boxes [K,6] float32 pixels as in compact()["boxes"], written in
+    their shortest text that reads back to the same float32."""
+    import csv
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f, lineterminator="\n")
+        w.writerow(["class", "y1", "x1", "z1", "y2", "x2", "z2"])
+        for cid, box in zip(class_ids, np.asarray(boxes, np.float32)):
+            w.writerow([int(cid)] + [str(v) for v in box])
+
+
+def evaluate_detections(detections, mrcnn_mask, image_shape, gt_class_ids, gt_masks, iou_threshold=0.5, labels=False,
+                        keep=None):
     """unmold + overlaps (one traversal of the boxes) -> AP for one image ->
     dict: mAP, precision, recall, ious (matched), iou / inter [K,G] of the kept
     detections (host), boxes, scores, class_ids, rows, status, area_pred,
     area_gt, and the device-side ``unmolded``.  Every result reaches the host
-    in one synchronising copy; raises on status RANGE."""
-    u = unmold_detections(detections, mrcnn_mask, image_shape, gt_masks=gt_masks)
+    in one synchronising copy; raises on status RANGE.
+
+    With ``labels`` also: ``labels`` (the device label volume [H,W,D] int32),
+    ``label_of`` (host, [max_inst]), ``pixelwise`` (precision, recall, f1, iou)
+    with its ``pixelwise_counts`` (tp, fp, fn), ``instance_dice`` (mean, std,
+    n) and ``detection_performance``.  ``keep`` (needs labels) restricts
+    ``rows`` and every per-row result, the AP included, to the listed rows.
+    label_of rides the packed copy as one more column; the three pixelwise
+    counts take one more 24-byte copy."""
+    u = unmold_detections(detections, mrcnn_mask, image_shape, gt_masks=gt_masks, labels=labels, keep=keep)
     iou, inter, _, area_gt = u.overlaps
     G = int(inter.shape[1])
     on_dev = torch.is_tensor(gt_class_ids) and gt_class_ids.is_cuda
     if on_dev and gt_class_ids.numel() != G:
         raise ValueError(f"gt_class_ids has {gt_class_ids.numel()} entries for {G} GT masks")
+    counts = pixelwise_counts(u.labels, gt_masks) if labels else None
     if G:
-        k = u._to_host(iou, inter, area_gt, gt_class_ids.reshape(-1) if on_dev else None)
+        k = u._to_host(iou, inter, area_gt, gt_class_ids.reshape(-1) if on_dev else None, label_of=u.label_of)
     else:
-        k = u.compact()
+        k = u._to_host(label_of=u.label_of)
         k.update(inter=np.zeros((len(k["rows"]), 0), np.int32), iou=np.zeros((len(k["rows"]), 0), np.float32),
                  area_gt=np.zeros(0, np.int32), gt_ids=np.zeros(0, np.int32))
     if on_dev:
@@ -309,6 +468,13 @@ def evaluate_detections(detections, mrcnn_mask, image_shape, gt_class_ids, gt_ma
         if len(gt_ids) != G:
             raise ValueError(f"gt_class_ids has {len(gt_ids)} entries for {G} GT masks")
     mAP, precision, recall, ious = compute_ap(k["iou"], k["class_ids"], gt_ids, iou_threshold)
-    return {"mAP": mAP, "precision": precision, "recall": recall, "ious": ious, "iou": k["iou"], "inter": k["inter"],
-            "boxes": k["boxes"], "scores": k["scores"], "class_ids": k["class_ids"], "rows": k["rows"],
-            "status": k["status"], "area_pred": k["area"], "area_gt": k["area_gt"], "unmolded": u}
+    out = {"mAP": mAP, "precision": precision, "recall": recall, "ious": ious, "iou": k["iou"], "inter": k["inter"],
+           "boxes": k["boxes"], "scores": k["scores"], "class_ids": k["class_ids"], "rows": k["rows"],
+           "status": k["status"], "area_pred": k["area"], "area_gt": k["area_gt"], "unmolded": u}
+    if labels:
+        tp, fp, fn = (int(v) for v in counts.cpu().numpy())
+        out.update(labels=u.labels, label_of=k["label_of"], pixelwise_counts=(tp, fp, fn),
+                   pixelwise=pixelwise_metrics(tp, fp, fn),
+                   instance_dice=instance_dice(k["inter"], k["area"], k["area_gt"]),
+                   detection_performance=detection_performance(k["inter"], k["area"], k["area_gt"]))
+    return out

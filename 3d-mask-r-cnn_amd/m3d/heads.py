@@ -897,13 +897,15 @@ class MaskRCNN:
                 "pooled": pooled, "mask_pooled": mpooled, "rpn_class": rpn_probs, "rpn_bbox": rpn_bbox}
 
     @torch.no_grad()
-    def evaluate(self, image, image_meta, gt_class_ids, gt_boxes, gt_masks, iou_threshold=0.5):
+    def evaluate(self, image, image_meta, gt_class_ids, gt_boxes, gt_masks, iou_threshold=0.5, labels=False):
         """The reference's MRCNN_EVALUATION for one image [1,H,W,D,Cin]: detect ->
         unmold_detections -> mask overlaps against gt_masks [H,W,D,G] (or
         [1,H,W,D,G]; uint8, G innermost) -> compute_ap (m3d.evaluate).  Returns
         evaluate_detections' dict (mAP, precision, recall, ious, iou, ...) plus
         ``detections`` and ``mrcnn_mask``.  gt_boxes is accepted for the
-        reference's signature; the mask IoU does not read it."""
+        reference's signature; the mask IoU does not read it.  ``labels``: also
+        the instance label volume and the pixelwise / Dice / detection metrics
+        (evaluate_detections)."""
         from .evaluate import evaluate_detections
         ops._dev(image, image_meta, gt_masks)
         if image.shape[0] != 1:
@@ -912,6 +914,69 @@ class MaskRCNN:
         if torch.is_tensor(gt_class_ids) and gt_class_ids.dim() == 2:
             gt_class_ids = gt_class_ids[0]
         out = evaluate_detections(r["detections"][0], r["mrcnn_mask"][0], tuple(image.shape[1:4]), gt_class_ids,
-                                  gt_masks, iou_threshold)
+                                  gt_masks, iou_threshold, labels=labels)
         out["detections"], out["mrcnn_mask"] = r["detections"], r["mrcnn_mask"]
         return out
+
+    @torch.no_grad()
+    def evaluate_dataset(self, dataset, result_dir=None, image_ids=None, iou_threshold=0.5):
+        """The reference's MRCNN_EVALUATION loop over a prepared ToyDataset
+        (core/models.py:7165-7196 with the per-image report of 6099-6151): per
+        image load_image / load_data (the volume must have config.IMAGE_SHAPE:
+        nothing is resized), evaluate(labels=True), and with ``result_dir`` the
+        segmentation volume ``<name>.tiff`` ([D,H,W] pages of instance labels,
+        uint8 up to 255 detections, else uint16) and ``<name>.csv`` (class and
+        pixel box of each listed detection, in label order); ``name`` is the
+        image file's basename without its extension.  Returns {"rows": one
+        report dict per image, "summary": mean / std of the pixelwise F1 and of
+        the instance Dice, mean mask-level recall / precision, over the
+        images}.  The label stack is copied to the host once per image, only
+        when ``result_dir`` is set."""
+        import os
+
+        from .evaluate import write_detection_csv
+        from .model import compose_image_meta
+        from .tiff import imwrite
+        shape = tuple(int(v) for v in self.config.IMAGE_SHAPE)
+        if result_dir is not None:
+            os.makedirs(result_dir, exist_ok=True)
+        rows = []
+        for image_id in (dataset.image_ids if image_ids is None else image_ids):
+            image_id = int(image_id)
+            image = dataset.load_image(image_id)
+            if tuple(image.shape) != shape:
+                raise ValueError(f"image {image_id} has shape {tuple(image.shape)}, the model is built for {shape} "
+                                 "(evaluate_dataset does not resize)")
+            _, class_ids, masks = dataset.load_data(image_id)
+            H, W, D = shape[:3]
+            meta = compose_image_meta(image_id, shape, shape, (0, 0, 0, H, W, D), 1.0,
+                                      np.ones(self.config.NUM_CLASSES, np.int32))
+            out = self.evaluate(torch.from_numpy(image[None]).to(self.device),
+                                torch.from_numpy(meta[None]).to(self.device), class_ids.astype(np.int32), None,
+                                torch.from_numpy(np.ascontiguousarray(masks != 0).view(np.uint8)).to(self.device),
+                                iou_threshold, labels=True)
+            name = os.path.splitext(os.path.basename(str(dataset.image_info[image_id]["path"])))[0]
+            if result_dir is not None:
+                imwrite(os.path.join(result_dir, name + ".tiff"), out["unmolded"].label_stack().cpu().numpy())
+                write_detection_csv(os.path.join(result_dir, name + ".csv"), out["class_ids"], out["boxes"])
+            n_pred, n_gt = len(out["rows"]), masks.shape[-1]
+            row = {"name": name, "pred_inst": n_pred}
+            if n_gt == 0 and n_pred == 0:                       # the reference's all-zero report
+                row.update(ap50=0.0, prec50=0.0, rec50=0.0, miou=0.0)
+            else:
+                ious = np.asarray(out["ious"], np.float32)
+                row.update(ap50=float(out["mAP"]), prec50=float(out["precision"]), rec50=float(out["recall"]),
+                           miou=float(np.nanmean(ious)) if ious.size else 0.0)
+            px, dice, det = out["pixelwise"], out["instance_dice"], out["detection_performance"]
+            row.update(px_precision=px[0], px_recall=px[1], px_f1=px[2], px_iou=px[3], dice_mean=dice[0],
+                       dice_std=dice[1], dice_n=dice[2], det_tp=det["tp"], det_fp=det["fp"], det_fn=det["fn"],
+                       det_recall=det["recall"], det_precision=det["precision"])
+            rows.append(row)
+
+        def stat(fn, key):
+            return float(fn([r[key] for r in rows])) if rows else 0.0
+        summary = {"images": len(rows), "pixelwise_f1_mean": stat(np.mean, "px_f1"),
+                   "pixelwise_f1_std": stat(np.std, "px_f1"), "instance_dice_mean": stat(np.mean, "dice_mean"),
+                   "instance_dice_std": stat(np.std, "dice_mean"), "recall_mean": stat(np.mean, "det_recall"),
+                   "precision_mean": stat(np.mean, "det_precision")}
+        return {"rows": rows, "summary": summary}

@@ -1,4 +1,5 @@
-"""Minimal multi-page TIFF reader (no scikit-image / tifffile in this image).
+"""Minimal multi-page TIFF reader, and a writer for label stacks (no
+scikit-image / tifffile in this image).
 
 The reference reads its volumes with ``skimage.io.imread`` (Z-first stacks,
 core/data_generators.py:1609-1610, written by ``io.imsave`` in
@@ -8,7 +9,8 @@ byte order, strip-organised, grayscale (or chunky multi-sample) pages of 8/16/
 Deflate (with horizontal predictor), and stacks the pages into a ``(Z, Y, X)``
 (or ``(Z, Y, X, S)``) array.  Tiled or LZW/JPEG files raise
 ``NotImplementedError``.  Pinned by tests/test_formats.py against files
-written by libtiff (tests/golden/h5src/make_tiff_fixtures.c).
+written by libtiff (tests/golden/h5src/make_tiff_fixtures.c).  ``imwrite``
+writes the evaluation's segmentation volumes (uint8 / uint16 pages).
 """
 from __future__ import annotations
 
@@ -126,3 +128,36 @@ def imread(path) -> np.ndarray:
     if not pages:
         raise ValueError(f"{path}: no image pages")
     return pages[0] if len(pages) == 1 else np.stack(pages)
+
+
+def imwrite(path, stack) -> None:
+    """uint8 / uint16 ``[pages, rows, cols]`` -> an uncompressed little-endian
+    baseline TIFF: one IFD and one strip per page, one sample per pixel,
+    ``minisblack`` (what the reference's ``imsave`` of its (D,H,W) label stack
+    holds, core/models.py:7072-7079).  Readable by ``imread`` above."""
+    a = np.asarray(stack)
+    if a.ndim != 3 or a.dtype not in (np.uint8, np.uint16) or 0 in a.shape:
+        raise ValueError(f"imwrite takes a non-empty uint8 / uint16 [pages, rows, cols] array, got {a.dtype} "
+                         f"{a.shape}")
+    pages, rows, cols = a.shape
+    a = np.ascontiguousarray(a.astype(a.dtype.newbyteorder("<"), copy=False))
+    nbytes = rows * cols * a.dtype.itemsize
+    tags = 10
+    ifd_bytes = 2 + 12 * tags + 4
+    block = (nbytes + 1 & ~1) + ifd_bytes                       # the page's strip (padded to a word), then its IFD
+    if 8 + pages * block >= 1 << 32:
+        raise ValueError("imwrite: the stack does not fit a baseline (32-bit offset) TIFF")
+    with open(path, "wb") as f:
+        f.write(struct.pack("<2sHI", b"II", 42, 8 + (nbytes + 1 & ~1)))
+        for p in range(pages):
+            data = 8 + p * block
+            nxt = data + block + (nbytes + 1 & ~1) if p + 1 < pages else 0
+            f.write(a[p].tobytes())
+            if nbytes & 1:
+                f.write(b"\0")
+            entries = ((256, 4, cols), (257, 4, rows), (258, 3, 8 * a.dtype.itemsize), (259, 3, 1), (262, 3, 1),
+                       (273, 4, data), (277, 3, 1), (278, 4, rows), (279, 4, nbytes), (339, 3, 1))
+            f.write(struct.pack("<H", tags))
+            for tag, typ, val in entries:                       # ascending tags; little-endian: a SHORT sits left
+                f.write(struct.pack("<HHII", tag, typ, 1, val))
+            f.write(struct.pack("<I", nxt))

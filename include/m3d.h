@@ -841,6 +841,36 @@ int m3d_unmold_paste(const uint8_t* small, const int32_t* box_i, const int32_t* 
 int m3d_mask_areas(const uint8_t* gt_masks, int64_t H, int64_t W, int64_t D, int64_t G, int32_t* area_gt,
                    m3d_stream_t s);
 
+/* The segmentation volume and its pixelwise counts (MRCNN_EVALUATION's
+ * seg[full > 0.5] = j + 1, core/models.py:7023-7087, and _pixelwise_metrics,
+ * 6153-6164), from the outputs of the entries above; run after
+ * m3d_unmold_finalize.
+ *   m3d_unmold_labels    a row is listed when its status is not NOT_KEPT and
+ *     (keep == NULL or keep[row] != 0; keep [max_inst] uint8).  label_of
+ *     [max_inst] int32 = 1 + the row's index among the listed rows in row
+ *     order, 0 for the others; a listed row whose status is not OK consumes
+ *     its label and paints nothing.  labels [H,W,D] int32 is zeroed, then every
+ *     voxel gets the largest label_of among the listed OK rows whose resized
+ *     mask is set there (the set voxels of m3d_unmold_paste): the later
+ *     detection wins, as in the reference's ascending loop.  A 32-bit atomic
+ *     max per set voxel: independent of arrival order.  max_inst <= 65535.
+ *   m3d_label_pixelwise  counts [3] int64 (zeroed first) = tp (labels > 0 and
+ *     any GT byte of the voxel set), fp (labels > 0, none set), fn (labels ==
+ *     0, any set).  G may be 0 (gt_masks unused: every labelled voxel is fp).
+ *   m3d_labels_stack     stack [D,H,W] uint8 (bytes_per_sample 1) or uint16
+ *     (2), the TIFF page order: stack[d,h,w] = labels[h,w,d] truncated to the
+ *     sample width.
+ * M3D_EINVAL before any launch: NULL pointers (keep may be NULL), non-positive
+ * m / H / W / D, H W D beyond 31 bits, negative max_inst or G, m^3 > 32768,
+ * max_inst > 65535, bytes_per_sample not 1 or 2. */
+int m3d_unmold_labels(const uint8_t* small, const int32_t* box_i, const int32_t* status, const double* stats,
+                      const uint8_t* keep, int64_t max_inst, int64_t m, int64_t H, int64_t W, int64_t D,
+                      int32_t* label_of, int32_t* labels, m3d_stream_t s);
+int m3d_label_pixelwise(const int32_t* labels, const uint8_t* gt_masks, int64_t H, int64_t W, int64_t D, int64_t G,
+                        int64_t* counts, m3d_stream_t s);
+int m3d_labels_stack(const int32_t* labels, int64_t H, int64_t W, int64_t D, int64_t bytes_per_sample, void* stack,
+                     m3d_stream_t s);
+
 /* ---------------------------------------------------------------------------
  * Elementwise / reduction kernels of the backbone-FPN-RPN graph.
  * ------------------------------------------------------------------------- */
