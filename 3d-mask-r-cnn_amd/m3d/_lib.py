@@ -191,6 +191,13 @@ _SIGS = {
     "m3d_unmold_labels": [c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p],
     "m3d_label_pixelwise": [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p],
     "m3d_labels_stack": [c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p],
+    "m3d_normalize_image_workspace_bytes": [c_i64, c_i64, c_i64, c_i32],
+    "m3d_normalize_image": [c_p, c_i32, c_i64, c_i64, c_i64, c_i32, c_p, c_p, c_p, c_sz, c_p],
+    "m3d_augment_image_workspace_bytes": [c_i64, c_i64, c_i64],
+    "m3d_augment_image": [c_p, c_i64, c_i64, c_i64, c_i32, c_f, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint32,
+                          c_p, c_p, c_sz, c_p],
+    "m3d_flip_masks_u8": [c_p, c_i64, c_i64, c_i64, c_i64, c_i32, c_p, c_p],
+    "m3d_flip_boxes": [c_p, c_i64, c_i64, c_i64, c_i64, c_i32, c_p, c_p],
     "m3d_maxpool3d_fwd": [c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32,
                           c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, c_p, c_p, c_p],
     "m3d_maxpool3d_bwd": [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32,
@@ -239,7 +246,8 @@ _RESTYPES = {"m3d_last_error": ctypes.c_char_p, "m3d_nms3d_workspace_bytes": c_s
              "m3d_conv3d_wino_tile_y": c_i32, "m3d_conv3d_wino_dgrad_tile_y": c_i32,
              "m3d_conv3d_wino_dgrad_tile_z": c_i32, "m3d_col_sums_batched_workspace_bytes": c_sz,
              "m3d_bn_train_few_rows_max": c_i64, "m3d_bn_train_workspace_bytes": c_sz,
-             "m3d_mask_out_bwd_workspace_bytes": c_sz}
+             "m3d_mask_out_bwd_workspace_bytes": c_sz, "m3d_normalize_image_workspace_bytes": c_sz,
+             "m3d_augment_image_workspace_bytes": c_sz}
 
 EXPORTED = tuple(_SIGS)
 

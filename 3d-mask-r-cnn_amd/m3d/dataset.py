@@ -149,8 +149,20 @@ class ToyDataset(Dataset):
                     raise ValueError(f"[load_dataset] bad '{nm}' at row {i}")
             self.add_image("dataset", image_id=i, path=img, seg_path=seg, cab_path=cab, m_path=msk)
 
-    def load_image(self, image_id, z_slice=None):
-        return normalize_image(imread(self.image_info[image_id]["path"]))
+    def load_image(self, image_id, z_slice=None, device=None, repeat=1):
+        """The normalised [H,W,D,1] float32 volume.  ``device=None``: numpy, on
+        the host.  With a device the raw stack is uploaded in its file dtype (1
+        or 2 bytes per voxel for 8- / 16-bit TIFFs) and normalised there
+        (m3d.preprocess.normalize_image; ``repeat=2`` is the reference's
+        evaluation input); returns a device tensor."""
+        raw = imread(self.image_info[image_id]["path"])
+        if device is None:
+            return normalize_image(raw)
+        import torch
+        from .preprocess import normalize_image as normalize_on_device
+        if raw.dtype not in (np.uint8, np.uint16, np.float32):
+            raw = raw.astype(np.float32)
+        return normalize_on_device(torch.from_numpy(np.ascontiguousarray(raw)).to(device), repeat=repeat)
 
     def load_data(self, image_id, masks_needed=True):
         """-> boxes [N,6] int32 (y1,x1,z1,y2,x2,z2) px, class_ids [N] int32,

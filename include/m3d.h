@@ -871,6 +871,61 @@ int m3d_label_pixelwise(const int32_t* labels, const uint8_t* gt_masks, int64_t 
 int m3d_labels_stack(const int32_t* labels, int64_t H, int64_t W, int64_t D, int64_t bytes_per_sample, void* stack,
                      m3d_stream_t s);
 
+/* The input pipeline: ToyDataset.load_image's normalisation
+ * (core/data_generators.py:1603-1630: transpose, np.percentile [1, 99], clip,
+ * mean / std, tanh(0.5 x)), the second normalisation of
+ * MrcnnGenerator.get_input_prediction (1227-1242) and apply_minimal_augs_3d
+ * (13-86), called per volume from RPNGenerator.data_generator (974-986,
+ * 1039-1042).
+ *   m3d_normalize_image  raw in file order (Z,Y,X), dtype M3D_DTYPE_*; out
+ *     [Y,X,Z] float32 (the network's [H,W,D]) with transpose 1.  With
+ *     transpose 0 raw is already laid out as out is (the three extents are
+ *     then those of that array, in its order).  The float64 evaluation of the
+ *     reference's formula, rounded once: p1 / p99 by numpy's `linear` method
+ *     (v = q / 100 (n - 1), lo = floor(v), g = v - lo, a = s[lo], b = s[min(lo
+ *     + 1, n - 1)], a + (b - a) g for g < 0.5, else b - (b - a) (1 - g)) from
+ *     the exact order statistics (radix selection on the device); mean and
+ *     population std of the volume clipped to [p1, p99] (exact integer sums
+ *     for the integer inputs, fp64 partials in a fixed order for float32);
+ *     out = (float) tanh(0.5 y) in fp64, y = (x - mean) / std when std > 0,
+ *     else x - mean.  stats: device double[6] = p1, p99, mean, std, the number
+ *     of non-finite inputs, 0 (reserved).  A volume with non-finite inputs is
+ *     counted in stats[4]; its output is unspecified.  Bit-identical run to
+ *     run.  workspace: m3d_normalize_image_workspace_bytes(Z, Y, X, dtype).
+ *   m3d_augment_image    in / out [H,W,D] float32, out of place: the flips of
+ *     flip_mask (bit 0 Y, bit 1 X, bit 2 Z), then for brightness_delta > 0
+ *     out = clip(x + (float)(-scale + 2 scale u), vmin, vmax) with vmin / vmax
+ *     the image's range and scale = (double) brightness_delta ((double) vmax -
+ *     (double) vmin + 1e-6), then for noise_std > 0 out += (float)(noise_std
+ *     sqrt(-2 ln(1 - u1)) cos(2 pi u2)), not clipped.  u from Philox4x32-10,
+ *     key (seed_lo, seed_hi), counter (idx_lo, idx_hi, stream, 0), idx the
+ *     voxel's linear index in out, stream 0 brightness / 1 Gaussian, u =
+ *     ((r0 >> 5) 2^26 + (r1 >> 6)) 2^-53 (u2 from r2, r3): a voxel's value
+ *     depends on (seed, idx) only.  The reference draws from an unseeded
+ *     RandomState; the formula and the distribution are matched, not its
+ *     stream.  workspace: m3d_augment_image_workspace_bytes(H, W, D), used
+ *     (and required) only when brightness_delta > 0.
+ *   m3d_flip_masks_u8    [H,W,D,G] bytes, G innermost, out of place.
+ *   m3d_flip_boxes       [N,6] pixel boxes (y1,x1,z1,y2,x2,z2), exclusive
+ *     ends: y1' = H - y2, y2' = H - y1, likewise x with W and z with D.
+ * M3D_EINVAL before any launch: NULL pointers, non-positive extents, voxel
+ * counts beyond 31 bits, an unknown dtype or flip_mask, a short or misaligned
+ * workspace, in == out. */
+#define M3D_DTYPE_U8 0
+#define M3D_DTYPE_U16 1
+#define M3D_DTYPE_F32 2
+size_t m3d_normalize_image_workspace_bytes(int64_t Z, int64_t Y, int64_t X, int32_t dtype);
+int m3d_normalize_image(const void* raw, int32_t dtype, int64_t Z, int64_t Y, int64_t X, int32_t transpose,
+                        float* out, double* stats, void* workspace, size_t ws_bytes, m3d_stream_t s);
+size_t m3d_augment_image_workspace_bytes(int64_t H, int64_t W, int64_t D);
+int m3d_augment_image(const float* in, int64_t H, int64_t W, int64_t D, int32_t flip_mask, float brightness_delta,
+                      double noise_std, uint32_t seed_lo, uint32_t seed_hi, float* out, void* workspace,
+                      size_t ws_bytes, m3d_stream_t s);
+int m3d_flip_masks_u8(const uint8_t* in, int64_t H, int64_t W, int64_t D, int64_t G, int32_t flip_mask,
+                      uint8_t* out, m3d_stream_t s);
+int m3d_flip_boxes(const float* in, int64_t N, int64_t H, int64_t W, int64_t D, int32_t flip_mask, float* out,
+                   m3d_stream_t s);
+
 /* ---------------------------------------------------------------------------
  * Elementwise / reduction kernels of the backbone-FPN-RPN graph.
  * ------------------------------------------------------------------------- */
