@@ -921,6 +921,7 @@ struct WgOut {
     int64_t pstride;      // floats per split (nbatch * K * N)
     int plain;
     int store;
+    const int* gate;      // row-sparse gate (bwd_weight_wino): the workgroup returns when *gate != 0; NULL: ungated
 };
 
 __device__ __forceinline__ void wg_put(const WgOut& o, float* C, float* P, int64_t idx, float v) {
@@ -933,7 +934,8 @@ __device__ __forceinline__ void wg_put(const WgOut& o, float* C, float* P, int64
 // C[b*bsc + r] += sum_{s = 0..splits-1} part[s][b][r]  (r < K*N), summed in s order
 __global__ __launch_bounds__(256) void wg_reduce_kernel(const float* __restrict__ part, int splits,
                                                         int64_t pstride, int64_t kn, int64_t bsc,
-                                                        float* __restrict__ C) {
+                                                        float* __restrict__ C, const int* gate) {
+    if (gate && *gate) return;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= pstride) return;
     float s = part[i];
@@ -965,7 +967,7 @@ static void wg_finish(const WgOut& o, int64_t splits, int64_t nbatch, int64_t K,
                       float* C, hipStream_t s) {
     if (!o.part) return;
     hipLaunchKernelGGL(wg_reduce_kernel, dim3(grid_for(o.pstride, 256)), dim3(256), 0, s, o.part, (int)splits,
-                       o.pstride, K * N, nbatch > 1 ? bsc : K * N, C);
+                       o.pstride, K * N, nbatch > 1 ? bsc : K * N, C, o.gate);
 }
 
 // `fresh`: C (nbatch contiguous K x N items) holds no prior value.  Called
@@ -1324,6 +1326,7 @@ __global__ __launch_bounds__(256, OCC) void x3_wgrad_kernel(const float* __restr
                                                             float* __restrict__ C, int64_t M, int K, int N,
                                                             int64_t m_per_split, int64_t bsa, int64_t bsb,
                                                             int64_t bsc, WgOut wo) {
+    if (wo.gate && *wo.gate) return;
     constexpr int BI = 128, BJ = 128, TI = 2, TJ = 2, BKM = 32;
     constexpr int PL = 128 * BKM * 2;                    // bytes per plane (128 rows x 64 B)
     __shared__ __attribute__((aligned(16))) char smem[6 * PL];
@@ -1449,6 +1452,7 @@ __global__ __launch_bounds__(256, OCC) void x3_wgrad64_kernel(const float* __res
                                                               float* __restrict__ C, int64_t M, int K, int N,
                                                               int64_t m_per_split, int64_t bsa, int64_t bsb,
                                                               int64_t bsc, WgOut wo) {
+    if (wo.gate && *wo.gate) return;
     constexpr int TI = 2, TJ = 2, BKM = 64;
     constexpr int SUB = 64 * 64;                         // one 32-m sub-image: 64 rows x 64 B
     constexpr int PL = 2 * SUB;                          // one plane of a 64-m chunk
@@ -1752,6 +1756,7 @@ __global__ __launch_bounds__(512, 1) void x3_wgrad_tr_kernel(const float* __rest
                                                              int N, int64_t m_per_split, int64_t bsa,
                                                              int64_t bsb, int64_t bsc, WgOut wo, X3wSK sk) {
     __shared__ __attribute__((aligned(16))) char smem[2 * W2_STAGE];
+    if (wo.gate && *wo.gate) return;
     if constexpr (SK) {
         // XCD-contiguous: the workgroups of one XCD take consecutive unit ranges.
         // The tn column tiles of one (batch, k tile) share their A rows, so they
@@ -1805,7 +1810,7 @@ static int wgrad_tr_env() {
 }
 
 static int launch_wgrad_tr(const float* A, const float* Bm, float* C, int64_t M, int K, int N, int nbatch,
-                           int64_t bsa, int64_t bsb, int64_t bsc, hipStream_t s, bool fresh) {
+                           int64_t bsa, int64_t bsb, int64_t bsc, hipStream_t s, bool fresh, const int* gate) {
     const int64_t tiles = (int64_t)((K + 255) / 256) * ((N + 255) / 256) * nbatch;
     const int64_t cus = num_cus();
     static constexpr int64_t minm = M3D_TUNE_X3W_TR_MINM;
@@ -1824,6 +1829,7 @@ static int launch_wgrad_tr(const float* A, const float* Bm, float* C, int64_t M,
         G = G / sk.tn * sk.tn;                        // whole groups of the tn column tiles
         if (G < sk.tn) G = sk.tn;
         WgOut wo{nullptr, 0, 0, 0};
+        wo.gate = gate;
         // a tile's steps may span two workgroups: stream-K always accumulates (never the owner store)
         const hipError_t fe = wg_settle(wo, 2, fresh, C, nbatch, K, N, s);
         if (fe != hipSuccess) return (int)fe;
@@ -1842,6 +1848,7 @@ static int launch_wgrad_tr(const float* A, const float* Bm, float* C, int64_t M,
     if (splits > max_splits) splits = max_splits;
     if (splits < 1) splits = 1;
     WgOut wo = wg_out(splits, nbatch, K, N);
+    wo.gate = gate;
     int64_t mper = (M + splits - 1) / splits;
     mper = (mper + W2_BK - 1) / W2_BK * W2_BK;
     splits = (M + mper - 1) / mper;
@@ -1862,9 +1869,10 @@ static int wgrad_x3_env() { return (x3_mask() >> 2) & 1; }
 // the result is C[b] = A[b]^T B[b]: owner store or zero-fill, see wg_settle.
 // Returns 0, or the hipError_t of a failed zero-fill (fresh only).
 static int launch_wgrad_x3(const float* A, const float* Bm, float* C, int64_t M, int K, int N, int nbatch,
-                           int64_t bsa, int64_t bsb, int64_t bsc, hipStream_t s, bool fresh = false) {
+                           int64_t bsa, int64_t bsb, int64_t bsc, hipStream_t s, bool fresh = false,
+                           const int* gate = nullptr) {
     if (wgrad_tr_env() && K >= 192 && N >= 192)
-        return launch_wgrad_tr(A, Bm, C, M, K, N, nbatch, bsa, bsb, bsc, s, fresh);
+        return launch_wgrad_tr(A, Bm, C, M, K, N, nbatch, bsa, bsb, bsc, s, fresh, gate);
     if (K <= 64 || N <= 64) {          // x3_wgrad64_kernel: 64x64 tiles, the m chunk over the waves
         const int64_t tiles = (int64_t)((K + 63) / 64) * ((N + 63) / 64);
         int64_t splits = (1024 + tiles * nbatch - 1) / (tiles * nbatch);
@@ -1873,6 +1881,7 @@ static int launch_wgrad_x3(const float* A, const float* Bm, float* C, int64_t M,
         if (splits > max_splits) splits = max_splits;
         if (splits < 1) splits = 1;
         WgOut wo = wg_out(splits, nbatch, K, N);
+        wo.gate = gate;
         int64_t mper = (M + splits - 1) / splits;
         mper = (mper + 63) / 64 * 64;
         splits = (M + mper - 1) / mper;
@@ -1890,6 +1899,7 @@ static int launch_wgrad_x3(const float* A, const float* Bm, float* C, int64_t M,
     if (splits > max_splits) splits = max_splits;
     if (splits < 1) splits = 1;
     WgOut wo = wg_out(splits, nbatch, K, N);
+    wo.gate = gate;
     int64_t mper = (M + splits - 1) / splits;
     mper = (mper + 31) / 32 * 32;
     splits = (M + mper - 1) / mper;
@@ -1948,6 +1958,9 @@ struct WinoGeom {
     // round-robin XCD dispatch gets contiguous tile ranges per XCD, so the
     // windows that overlap neighbouring tiles' stay in one L2
     int xcd;
+    // row-sparse gate (bwd_data_wino / bwd_weight_wino): a gated workgroup returns
+    // when *gate != 0; NULL (every other caller): ungated
+    const int* gate;
 };
 
 __device__ __forceinline__ int64_t wino_block(const WinoGeom& g) {
@@ -2071,6 +2084,7 @@ template <int NZ, bool X3O = false, bool HALO = false, int NYT = WNY>
 __global__ __launch_bounds__(256) void wino_input_kernel(const float* __restrict__ x, WinoGeom g,
                                                          int C, float* __restrict__ U) {
     constexpr int P = ZT<NZ>::P, PYt = ZT<NYT>::P;
+    if (g.gate && *g.gate) return;
     const int64_t i = wino_block(g) * blockDim.x + threadIdx.x;
     if (i >= g.T * C) return;
     const int c = (int)(i % C);
@@ -2267,6 +2281,7 @@ __device__ __forceinline__ void wino_output_body(const float* __restrict__ Mt, c
 template <int NZ, int NYT = WNY>
 __global__ __launch_bounds__(256) void wino_output_kernel(const float* __restrict__ Mt, WinoGeom g,
                                                           int N, Epi e) {
+    if (g.gate && *g.gate) return;
     wino_output_body<NZ, false, NYT>(Mt, g, N, e);
 }
 // depth-slab data gradient: interior planes into e.y, halo planes into e.yh
@@ -2482,6 +2497,7 @@ template <int NZ>
 __global__ __launch_bounds__(256) void wino_grad_kernel(const float* __restrict__ dz, WinoGeom g,
                                                         int N, float* __restrict__ DY) {
     constexpr int P = ZT<NZ>::P;
+    if (g.gate && *g.gate) return;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= g.T * N) return;
     const int n = (int)(i % N);
@@ -2533,8 +2549,10 @@ __global__ __launch_bounds__(256) void wino_grad_kernel(const float* __restrict_
 // dW[t][c][n] += (G^T (x) G^T (x) Gz^T) dWh[.][c][n]
 template <int NZ>
 __global__ __launch_bounds__(256) void wino_wgrad_out_kernel(const float* __restrict__ dWh, int C,
-                                                             int N, float* __restrict__ dw) {
+                                                             int N, float* __restrict__ dw,
+                                                             const int* gate) {
     constexpr int P = ZT<NZ>::P;
+    if (gate && *gate) return;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t CN = (int64_t)C * N;
     if (i >= CN) return;
@@ -2623,6 +2641,8 @@ struct X3G {
     int64_t psa = 0, psb = 0;     // plane strides (elements)
     int64_t bsa = 0, bsb = 0, bsc = 0;   // batch strides (elements)
     X3Epi ep = {};                // x3_gemm256_af_kernel only (zero: the plain C store)
+    const int* gate = nullptr;    // row-sparse gate: the workgroup returns when *gate != 0 (NULL: ungated)
+    const int* mlim = nullptr;    // row tiles starting at or past *mlim are skipped (NULL: all of M)
 };
 
 // byte offset of (row, chunk) in a 16-deep X3 plane: 32-B rows of two 16-B
@@ -2662,6 +2682,7 @@ __global__ __launch_bounds__(256, OCC) void x3_gemm_kernel(X3G g) {
     int64_t L = PERSIST ? (int64_t)blockIdx.x : (int64_t)blockIdx.x + (int64_t)gridDim.x * blockIdx.y;
     const int64_t Lstep = PERSIST ? (int64_t)gridDim.x : total;
     const int nk = g.K / BK;
+    if (g.gate && *g.gate) return;
     float* const Ts = reinterpret_cast<float*>(smem);
     int soff[CPT];
     uint32_t lrow[CPT];
@@ -2676,6 +2697,7 @@ __global__ __launch_bounds__(256, OCC) void x3_gemm_kernel(X3G g) {
         const int64_t bz = T / per_batch, Tt = T - bz * per_batch;
         const int64_t m0 = (Tt / nby) * BM;
         const int n0 = (int)(Tt % nby) * BN;
+        if (g.mlim && m0 >= *g.mlim) continue;
         __amdgpu_buffer_rsrc_t ra[3], rb[3];
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) {
@@ -2842,11 +2864,13 @@ __global__ __launch_bounds__(512, 1) void x3_gemm256_kernel(X3G g) {
     const int64_t per_batch = nbx * nby, total = per_batch * g.nbatch;
     const int64_t L = (int64_t)blockIdx.x + (int64_t)gridDim.x * blockIdx.y;
     if (L >= total) return;
+    if (g.gate && *g.gate) return;
     const int64_t xcd = L % 8, q8 = total / 8, r8 = total % 8;
     const int64_t T = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + L / 8;
     const int64_t bz = T / per_batch, Tt = T - bz * per_batch;
     const int64_t m0 = (Tt / nby) * 256;
     const int64_t n0 = (Tt % nby) * 256;
+    if (g.mlim && m0 >= *g.mlim) return;
     // descriptors start at the tile's first row: rows past M read zeros
     __amdgpu_buffer_rsrc_t rs[6];
 #pragma unroll
@@ -2986,11 +3010,13 @@ __global__ __launch_bounds__(512, 1) void x3_gemm256_af_kernel(X3G g) {
     const int64_t per_batch = nbx * nby, total = per_batch * g.nbatch;
     const int64_t L = (int64_t)blockIdx.x + (int64_t)gridDim.x * blockIdx.y;
     if (L >= total) return;
+    if (g.gate && *g.gate) return;
     const int64_t xcd = L % 8, q8 = total / 8, r8 = total % 8;
     const int64_t T = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + L / 8;
     const int64_t bz = T / per_batch, Tt = T - bz * per_batch;
     const int64_t m0 = (Tt / nby) * 256;
     const int64_t n0 = (Tt % nby) * 256;
+    if (g.mlim && m0 >= *g.mlim) return;
     const int nk = g.K / G2_BK;
     // A: fp32 rows from the tile's first row (rows past M and steps past nk read zeros)
     const __amdgpu_buffer_rsrc_t ra = make_rsrc(g.af + bz * g.bsa + m0 * g.K, (uint64_t)(g.M - m0) * g.K * 4);
@@ -4375,6 +4401,9 @@ extern "C" int32_t m3d_conv3d_wino_tile_y(void) { return WNY; }
 extern "C" int32_t m3d_conv3d_wino_dgrad_tile_y(void) { return wino_dgrad_ny(); }
 extern "C" int32_t m3d_conv3d_wino_dgrad_tile_z(void) { return wino_dgrad_nz(); }
 
+// the row-sparse header behind a call's layout (rs_hdr, below) for dz of `rows` voxel rows
+static size_t rs_hdr_bytes(int64_t rows);
+
 extern "C" size_t m3d_conv3d_wino_workspace_bytes(int64_t B, int64_t H, int64_t W, int64_t D,
                                                   int64_t OD, int64_t Cin, int64_t Cout) {
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
@@ -4395,17 +4424,22 @@ extern "C" size_t m3d_conv3d_wino_workspace_bytes(int64_t B, int64_t H, int64_t 
         const size_t b = wt + al(eb * P * (size_t)Cin * Cout) + (um1 > um2 ? um1 : um2);
         best = b > best ? b : best;
     }
-    return best;
+    return best + rs_hdr_bytes(B * H * W * (D > OD ? D : OD));
 }
 
 struct WinoWs { float *V, *U, *M, *WT; };
-// bytes wino_ws lays out for geometry g, operand widths C1 (U) / C2 (M) and the tile (nz, ny)
-static size_t wino_ws_need(const WinoGeom& g, int64_t C1, int64_t C2, int nz, int ny) {
+// bytes wino_ws lays out for geometry g, operand widths C1 (U) / C2 (M) and the tile (nz, ny);
+// the row-sparse header follows at this offset
+static size_t wino_ws_layout(const WinoGeom& g, int64_t C1, int64_t C2, int nz, int ny) {
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t P = (size_t)wino_points(nz, ny);
     const size_t eb = gemm_x3_env() ? 6 : 4;
     const size_t wt = gemm_x3_env() ? al(sizeof(float) * 27 * (size_t)C1 * C2) : 0;
     return wt + al(eb * P * (size_t)C1 * C2) + al(eb * P * (size_t)g.T * C1) + al(4 * P * (size_t)g.T * C2);
+}
+// what a data-gradient call checks: its layout and the header for dz rows of depth max(D, OD)
+static size_t wino_ws_need(const WinoGeom& g, int64_t C1, int64_t C2, int nz, int ny) {
+    return wino_ws_layout(g, C1, C2, nz, ny) + rs_hdr_bytes((int64_t)g.B * g.H * g.W * (g.D > g.Din ? g.D : g.Din));
 }
 // the data gradient's own workspace at tile_y (0: the library default): the
 // layout bwd_data_wino checks (dz transformed over Cout, dx's points over Cin)
@@ -4458,8 +4492,9 @@ static int x3_af32_env() { return (x3_mask() >> 4) & 1; }
 // the P point GEMMs M[xi] = U[xi] V[xi] on split planes (U: T x K, V: N x K);
 // af32: U is fp32 [P][T][K] (split in the GEMM's LDS store)
 static void wino_gemm_x3(const WinoWs& ws, int64_t T, int K, int N, int P, hipStream_t s,
-                         bool af32 = false) {
+                         bool af32 = false, const int* gate = nullptr, const int* mlim = nullptr) {
     X3G q{};                   // (value-initialised: q.ep.on = 0, the plain C store)
+    q.gate = gate; q.mlim = mlim;
     q.a = reinterpret_cast<const unsigned short*>(ws.U);
     q.af = ws.U;
     q.b = reinterpret_cast<const unsigned short*>(ws.V);
@@ -4833,7 +4868,7 @@ static int bwd_data_wino(const float* dz, const float* w, int64_t B, int64_t H, 
                          int64_t Cin, int64_t Cout, int64_t OD, int32_t pz, float* dx, int32_t accumulate,
                          void* workspace, size_t ws_bytes, hipStream_t s, float* dx_halo = nullptr,
                          int hlo = 0, bool v_ready = false, const Epi* fb = nullptr, int ny = 0,
-                         const void* v_ext = nullptr);
+                         const void* v_ext = nullptr, int rs_mode = 0);
 
 // The same two entry points for convs that share one kernel across calls (the
 // RPN head's rpn_conv_shared1 on P2..P6, core/models.py:512-557): with
@@ -4997,6 +5032,397 @@ extern "C" int m3d_conv3d_bwd_data_wino_xv(const float* dz, const float* w, int6
                          false, nullptr, ny, v);
 }
 
+// ---- row-sparse output gradients --------------------------------------------
+// The RPN loss leaves a gradient only on the sampled anchors, so the dz that
+// reaches rpn_conv_shared1 has a few hundred non-zero voxel rows out of 10^5.
+// bwd_data_wino / bwd_weight_wino scan dz on the device (a probe of evenly
+// spaced rows first: a dense dz costs no pass over the tensor), and either run
+// the Winograd launches (state DENSE) or a gather -> split GEMM -> scatter
+// over the active rows only (state SPARSE).  Both sets of launches are always
+// enqueued -- the step is replayed from a graph -- and every workgroup of the
+// set that is not due returns on a gate word of the header below.
+// Header (ints) behind the call's [WT][V][U][M] layout:
+//   h[RS_STATE] 0 undecided (after the probe) / RS_DENSE / RS_SPARSE
+//   h[RS_SKIP_DENSE] != 0: the dense kernels return; h[RS_SKIP_SPARSE] != 0: the sparse ones
+//   h[RS_N] active rows (SPARSE);  h[RS_PROBE] != 0: the probe found dz dense (written by the probe
+//   alone: the scan kernels read it, and never a word that one of them writes);
+//   idx[RS_CAP_MAX] the active rows, ascending;
+//   blk[rows / 64] active rows per 64-row group;  slot[rows] row -> compact slot or -1
+constexpr int RS_CAP_MAX = 4096;        // most active rows the sparse path takes ...
+constexpr int RS_CAP_DIV = 32;          // ... and at most rows / 32
+constexpr int RS_PROBE_ROWS = 256;      // rows the probe reads
+constexpr int RS_PROBE_DIV = 8;         // probe: DENSE when more than 1 / 8 of them are active
+constexpr int RS_BLK = 64;              // rows per scan block
+// RS_AUTO attempts the sparse path when the layer's direct-equivalent work 2 * 27 * rows * Cin * Cout reaches
+// this.  A dense call pays 18-30 us for the attempt (probe, two scan launches that return, the gated sparse
+// launches; DESIGN.md 5, scripts/rowsparse_overhead.py), which is to stay near 2 % of the call: 0.9 TFLOP
+// admits rpn_conv_shared1 on P2 at 128^3 (0.93 TFLOP: 0.9-1.7 % / 1.6-2.4 % of its dense data / weight
+// gradient) and leaves out fpn_p2 (0.46 TFLOP: 2.9 % / 3.2 %) and P3 (0.23 TFLOP).  The benchmark's P2
+// sits 3 % above the threshold: a smaller volume runs dense (DESIGN.md 5 says what would lift that)
+constexpr double RS_MIN_FLOP = 9e11;
+enum { RS_STATE = 0, RS_SKIP_DENSE = 1, RS_SKIP_SPARSE = 2, RS_N = 3, RS_PROBE = 4, RS_HDR_INTS = 64 };
+enum { RS_UNDECIDED = 0, RS_DENSE = 1, RS_SPARSE = 2 };
+
+// rs_mode, a per-call argument of m3d_conv3d_bwd_data_wino_rs / m3d_conv3d_bwd_weight_wino_ux (a test
+// and A/B hook; the library holds no mode, every other entry point runs RS_AUTO): RS_AUTO attempts from
+// RS_MIN_FLOP on, RS_OFF runs exactly the dense launches, ungated, RS_ALWAYS attempts at every size.
+enum { RS_AUTO = 0, RS_OFF = 1, RS_ALWAYS = 2 };
+
+static size_t rs_al(size_t b) { return (b + 255) & ~(size_t)255; }
+static size_t rs_hdr_bytes(int64_t rows) {
+    return rs_al(sizeof(int) * (RS_HDR_INTS + RS_CAP_MAX)) + rs_al(sizeof(int) * (size_t)((rows + RS_BLK - 1) / RS_BLK)) +
+           rs_al(sizeof(int) * (size_t)rows);
+}
+struct RsHdr { int *h, *idx, *blk, *slot; };
+static RsHdr rs_hdr(void* base, int64_t rows) {
+    RsHdr r{};
+    char* p = static_cast<char*>(base);
+    r.h = reinterpret_cast<int*>(p);
+    r.idx = r.h + RS_HDR_INTS;
+    p += rs_al(sizeof(int) * (RS_HDR_INTS + RS_CAP_MAX));
+    r.blk = reinterpret_cast<int*>(p);
+    p += rs_al(sizeof(int) * (size_t)((rows + RS_BLK - 1) / RS_BLK));
+    r.slot = reinterpret_cast<int*>(p);
+    return r;
+}
+static int rs_cap(int64_t rows) {
+    const int64_t c = rows / RS_CAP_DIV;
+    return (int)(c > RS_CAP_MAX ? RS_CAP_MAX : c);
+}
+// whether this call scans dz at all (host side: shapes and the process mode only)
+static bool rs_attempt(int mode, int64_t rows, int64_t Cin, int64_t Cout) {
+    if (mode == RS_OFF || !gemm_x3_env() || !wgrad_x3_env()) return false;
+    if (rs_cap(rows) < 1 || rows > 0x7FFFFFFF) return false;
+    return mode == RS_ALWAYS || 2.0 * 27.0 * (double)rows * (double)Cin * (double)Cout >= RS_MIN_FLOP;
+}
+
+// this lane's part of "row has an element != 0" (-0.0f is not, a NaN is), C % 4 == 0
+__device__ __forceinline__ bool rs_lane_active(const float* __restrict__ row, int C, int lane) {
+    bool a = false;
+    for (int c = lane * 4; c < C; c += 256) {
+        const float4 v = *reinterpret_cast<const float4*>(row + c);
+        a |= (v.x != 0.0f) | (v.y != 0.0f) | (v.z != 0.0f) | (v.w != 0.0f);
+    }
+    return a;
+}
+
+// one workgroup of 16 waves: RS_PROBE_ROWS evenly spaced rows, 16 per wave
+__global__ __launch_bounds__(1024) void rs_probe_kernel(const float* __restrict__ dz, int64_t rows, int C,
+                                                        int* __restrict__ h) {
+    __shared__ int cnt[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int ns = rows < RS_PROBE_ROWS ? (int)rows : RS_PROBE_ROWS;
+    unsigned m = 0;
+#pragma unroll
+    for (int k = 0; k < RS_PROBE_ROWS / 16; ++k) {
+        const int i = wave * (RS_PROBE_ROWS / 16) + k;
+        bool a = false;
+        // evenly spaced, each sample 37 rows further along than the last: a plain stride is a multiple of
+        // the depth at the step's shapes and would read one z plane and one x phase only
+        if (i < ns) a = rs_lane_active(dz + (((int64_t)i * rows / ns + (int64_t)i * 37) % rows) * C, C, lane);
+        m |= (a ? 1u : 0u) << k;
+    }
+    int c = 0;
+#pragma unroll
+    for (int k = 0; k < RS_PROBE_ROWS / 16; ++k) c += __ballot((m >> k) & 1u) != 0ull ? 1 : 0;
+    if (lane == 0) cnt[wave] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int a = 0;
+        for (int w = 0; w < 16; ++w) a += cnt[w];
+        const bool dense = a * RS_PROBE_DIV > ns;
+        h[RS_PROBE] = dense ? 1 : 0;
+        h[RS_STATE] = dense ? RS_DENSE : RS_UNDECIDED;
+        h[RS_SKIP_DENSE] = 0;
+        h[RS_SKIP_SPARSE] = 1;
+        h[RS_N] = 0;
+    }
+}
+
+// slot[row] = row active (0 / 1), blk[block] = active rows of the block's RS_BLK rows
+__global__ __launch_bounds__(256) void rs_flag_kernel(const float* __restrict__ dz, int64_t rows, int C,
+                                                      const int* __restrict__ h, int* __restrict__ blk,
+                                                      int* __restrict__ slot) {
+    if (h[RS_PROBE]) return;
+    __shared__ int cnt[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t r0 = (int64_t)blockIdx.x * RS_BLK + wave * 16;
+    unsigned m = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        bool a = false;
+        if (r0 + k < rows) a = rs_lane_active(dz + (r0 + k) * C, C, lane);
+        m |= (a ? 1u : 0u) << k;
+    }
+    int c = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const int act = __ballot((m >> k) & 1u) != 0ull ? 1 : 0;
+        if (lane == 0 && r0 + k < rows) slot[r0 + k] = act;
+        c += act;
+    }
+    if (lane == 0) cnt[wave] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) blk[blockIdx.x] = cnt[0] + cnt[1] + cnt[2] + cnt[3];
+}
+
+// Everything between the scan's flags and the sparse GEMM, in one launch (each launch a dense call
+// makes for nothing costs it about 3.5 us).  Every workgroup sums blk itself -- the count n, hence the
+// state, and the count before its own rows -- so no launch stands between the flags and their prefix.
+// Block ranges: [0, nb_idx) 256 rows each: slot[row] = compact slot or -1, idx[slot] = row (ascending:
+// slots follow the row order), and the active rows gathered, dzc[slot] = dz[row] and, for the weight
+// gradient, xg[tap][slot] = x at the tap's input voxel ('same' padding: zero outside);
+// then nb_zero blocks zero rows n..cap of dzc / xg; then (data gradient) the three bf16 planes of w.
+struct RsPack {
+    const float* dz = nullptr;
+    int64_t rows = 0;
+    int C = 0, cap = 0;
+    int* h = nullptr;
+    const int* blk = nullptr;
+    int* slot = nullptr;
+    int* idx = nullptr;
+    float* dzc = nullptr;                  // [cap][C]
+    const float* x = nullptr;              // weight gradient: x [B][H][W][D][Cx] -> xg [27][cap][Cx]
+    float* xg = nullptr;
+    int H = 0, W = 0, D = 0, OD = 0, pz = 0, Cx = 0;
+    const float* w = nullptr;              // data gradient: w (nw elements) -> planes wp [3][nw]
+    unsigned short* wp = nullptr;
+    int64_t nw = 0;
+    unsigned nb_idx = 0, nb_zero = 0;
+};
+constexpr int RS_SPLIT_PER = 2048;         // elements of w per split block
+
+__device__ __forceinline__ void rs_copy_row(const float* __restrict__ s, float* __restrict__ d, int C, int lane,
+                                            bool on) {
+    for (int c = lane * 4; c < C; c += 256) {
+        float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (on) v = *reinterpret_cast<const float4*>(s + c);
+        *reinterpret_cast<float4*>(d + c) = v;
+    }
+}
+
+__global__ __launch_bounds__(256) void rs_pack_kernel(RsPack p) {
+    // the probe's verdict, in a word no launch of this kernel writes: the exit is the same for every wave
+    // of every workgroup (block 0 publishes the final state below, in words this kernel never reads)
+    if (p.h[RS_PROBE]) return;
+    __shared__ int red[2][4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t nblk = (p.rows + RS_BLK - 1) / RS_BLK;
+    const bool ib = blockIdx.x < p.nb_idx;
+    const int64_t g0 = ib ? (int64_t)blockIdx.x * 4 : 0;        // this block's first 64-row group
+    int tot = 0, pre = 0;
+    for (int64_t i = tid; i < nblk; i += 256) {
+        const int c = p.blk[i];
+        tot += c;
+        if (i < g0) pre += c;
+    }
+#pragma unroll
+    for (int o = 32; o; o >>= 1) {
+        tot += __shfl_xor(tot, o);
+        pre += __shfl_xor(pre, o);
+    }
+    if (lane == 0) { red[0][wave] = tot; red[1][wave] = pre; }
+    __syncthreads();
+    const int n = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+    const bool sparse = n <= p.cap;
+    if (blockIdx.x == 0 && tid == 0) {
+        p.h[RS_STATE] = sparse ? RS_SPARSE : RS_DENSE;
+        p.h[RS_SKIP_DENSE] = sparse ? 1 : 0;
+        p.h[RS_SKIP_SPARSE] = sparse ? 0 : 1;
+        p.h[RS_N] = sparse ? n : 0;
+    }
+    if (!sparse) return;
+    if (ib) {
+        const int64_t g = g0 + wave;
+        if (g >= nblk) return;
+        int base = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+        for (int q = 0; q < wave; ++q) base += p.blk[g0 + q];
+        const int64_t r = g * RS_BLK + lane;
+        const bool act = r < p.rows && p.slot[r] != 0;
+        unsigned long long m = __ballot(act);
+        const int s = base + __popcll(m & ((1ull << lane) - 1ull));
+        if (r < p.rows) p.slot[r] = act ? s : -1;
+        if (act) p.idx[s] = (int)r;                    // s < n <= cap <= RS_CAP_MAX
+        for (int k = 0; m; ++k) {                      // the group's active rows, one after the other
+            const int j = __ffsll(m) - 1;
+            m &= m - 1;
+            const int64_t row = g * RS_BLK + j;
+            const int sk = base + k;
+            if (!p.dzc) break;                         // (the scan alone)
+            rs_copy_row(p.dz + row * p.C, p.dzc + (int64_t)sk * p.C, p.C, lane, true);
+            if (!p.xg) continue;
+            int64_t t = row;
+            const int zo = (int)(t % p.OD); t /= p.OD;
+            const int xo = (int)(t % p.W); t /= p.W;
+            const int yo = (int)(t % p.H);
+            const int64_t b = t / p.H;
+            // all 27 taps' loads of a 256-channel chunk in flight before the stores (one wave per row:
+            // tap after tap the copies ran at one load latency each, 54 us of the 128^3 P2 call)
+            for (int c = lane * 4; c < p.Cx; c += 256) {
+                float4 v[27];
+#pragma unroll
+                for (int tap = 0; tap < 27; ++tap) {
+                    const int yi = yo + tap / 9 - 1, xi = xo + (tap / 3) % 3 - 1, zi = zo + tap % 3 - p.pz;
+                    const bool in = (unsigned)yi < (unsigned)p.H && (unsigned)xi < (unsigned)p.W &&
+                                    (unsigned)zi < (unsigned)p.D;
+                    v[tap] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                    if (in)
+                        v[tap] = *reinterpret_cast<const float4*>(
+                            p.x + (((b * p.H + yi) * p.W + xi) * p.D + zi) * p.Cx + c);
+                }
+#pragma unroll
+                for (int tap = 0; tap < 27; ++tap)
+                    *reinterpret_cast<float4*>(p.xg + ((int64_t)tap * p.cap + sk) * p.Cx + c) = v[tap];
+            }
+        }
+        return;
+    }
+    const unsigned bz = blockIdx.x - p.nb_idx;
+    if (bz < p.nb_zero) {
+        const int r = (int)bz * 4 + wave;
+        if (r < n || r >= p.cap) return;
+        rs_copy_row(p.dz, p.dzc + (int64_t)r * p.C, p.C, lane, false);
+        if (p.xg)
+            for (int tap = 0; tap < 27; ++tap)
+                rs_copy_row(p.x, p.xg + ((int64_t)tap * p.cap + r) * p.Cx, p.Cx, lane, false);
+        return;
+    }
+    const int64_t i0 = (int64_t)(bz - p.nb_zero) * RS_SPLIT_PER + tid;
+#pragma unroll
+    for (int k = 0; k < RS_SPLIT_PER / 256; ++k) {
+        const int64_t i = i0 + k * 256;
+        if (i >= p.nw) break;
+        uint32_t hi, mi, lo;
+        split3(p.w[i], hi, mi, lo);
+        p.wp[i] = (unsigned short)hi;
+        p.wp[p.nw + i] = (unsigned short)mi;
+        p.wp[2 * p.nw + i] = (unsigned short)lo;
+    }
+}
+
+// probe, flags, pack: q holds the pack's operands (x / xg or w / wp, dzc); the rest is filled in here
+static void rs_scan(const float* dz, int64_t rows, int C, int cap, const RsHdr& hd, RsPack q, hipStream_t s) {
+    const int64_t nblk = (rows + RS_BLK - 1) / RS_BLK;
+    q.dz = dz; q.rows = rows; q.C = C; q.cap = cap;
+    q.h = hd.h; q.blk = hd.blk; q.slot = hd.slot; q.idx = hd.idx;
+    q.nb_idx = (unsigned)((nblk + 3) / 4);
+    q.nb_zero = q.dzc ? (unsigned)((cap + 3) / 4) : 0;
+    const unsigned nb_split = (unsigned)((q.nw + RS_SPLIT_PER - 1) / RS_SPLIT_PER);
+    hipLaunchKernelGGL(rs_probe_kernel, dim3(1), dim3(1024), 0, s, dz, rows, C, hd.h);
+    hipLaunchKernelGGL(rs_flag_kernel, dim3((unsigned)nblk), dim3(256), 0, s, dz, rows, C, hd.h, hd.blk, hd.slot);
+    hipLaunchKernelGGL(rs_pack_kernel, dim3(q.nb_idx + q.nb_zero + nb_split), dim3(256), 0, s, q);
+}
+
+// The scan alone (tests): ws receives the header of the layout above for `rows` rows.
+extern "C" size_t m3d_conv3d_rowsparse_scan_bytes(int64_t rows) { return rows > 0 ? rs_hdr_bytes(rows) : 0; }
+extern "C" int m3d_conv3d_rowsparse_scan(const float* dz, int64_t rows, int64_t C, int32_t cap, void* ws,
+                                         size_t ws_bytes, m3d_stream_t s) {
+    if (rows <= 0 || rows > 0x7FFFFFFF || C <= 0 || C % 4) return einval("rowsparse_scan: rows > 0 and C a positive multiple of 4");
+    if (cap < 0 || cap > RS_CAP_MAX) return einval("rowsparse_scan: cap must be in [0, 4096]");
+    if (!dz || !ws || ws_bytes < rs_hdr_bytes(rows)) return einval("rowsparse_scan: workspace missing or too small");
+    rs_scan(dz, rows, (int)C, cap, rs_hdr(ws, rows), RsPack{}, st(s));
+    return check_launch("rowsparse_scan");
+}
+
+// dx[v][:] (+)= sum over the 27 taps, in tap order, of ct[slot(dz row of the tap)][tap][:]
+// where that row is inside dz and active: dx voxel (y, x, z) takes tap (ky, kx, kz)
+// from dz (y - ky + 1, x - kx + 1, z - kz + pz).  A workgroup owns 8 consecutive
+// voxels; a voxel without an active neighbour is zero-filled (left as it is
+// under accumulate).
+constexpr int RS_VOX = 8;
+__global__ __launch_bounds__(256) void rs_dgrad_out_kernel(const float* __restrict__ ct, int64_t nvox, int H, int W,
+                                                           int D, int OD, int pz, int C, int accumulate,
+                                                           const int* __restrict__ h,
+                                                           const int* __restrict__ slot, float* __restrict__ dx) {
+    if (h[RS_SKIP_SPARSE]) return;
+    __shared__ int ss[RS_VOX * 27];
+    __shared__ int hit[RS_VOX];
+    const int tid = threadIdx.x;
+    const int64_t v0 = (int64_t)blockIdx.x * RS_VOX;
+    if (tid < RS_VOX) hit[tid] = 0;
+    __syncthreads();
+    if (tid < RS_VOX * 27) {
+        const int j = tid / 27, tap = tid % 27, ky = tap / 9, kx = (tap / 3) % 3, kz = tap % 3;
+        int sl = -1;
+        int64_t t = v0 + j;
+        if (t < nvox) {
+            const int z = (int)(t % D); t /= D;
+            const int xx = (int)(t % W); t /= W;
+            const int y = (int)(t % H);
+            const int64_t b = t / H;
+            const int yo = y - ky + 1, xo = xx - kx + 1, zo = z - kz + pz;
+            if ((unsigned)yo < (unsigned)H && (unsigned)xo < (unsigned)W && (unsigned)zo < (unsigned)OD)
+                sl = slot[((b * H + yo) * W + xo) * OD + zo];
+        }
+        ss[tid] = sl;
+        if (sl >= 0) hit[j] = 1;
+    }
+    __syncthreads();
+    const int L = C / 4;
+    for (int q = tid; q < RS_VOX * L; q += 256) {
+        const int j = q / L, c = (q % L) * 4;
+        if (v0 + j >= nvox) break;
+        float* o = dx + (v0 + j) * C + c;
+        if (!hit[j]) {
+            if (!accumulate) *reinterpret_cast<float4*>(o) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            continue;
+        }
+        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (accumulate) a = *reinterpret_cast<const float4*>(o);
+        for (int tap = 0; tap < 27; ++tap) {
+            const int sl = ss[j * 27 + tap];
+            if (sl < 0) continue;
+            const float4 v = *reinterpret_cast<const float4*>(ct + ((int64_t)sl * 27 + tap) * C + c);
+            a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+        }
+        *reinterpret_cast<float4*>(o) = a;
+    }
+}
+
+// bytes the sparse paths lay out from the U region on (both regions belong to
+// the path that runs): data gradient dzc [cap][Cout], w planes, ct [cap][27][Cin];
+// weight gradient dzc [cap][Cout], xg [27][cap][Cin]
+static size_t rs_dgrad_bytes(int cap, int64_t Cin, int64_t Cout) {
+    return rs_al(4 * (size_t)cap * Cout) + rs_al(6 * 27 * (size_t)Cin * Cout) + rs_al(4 * (size_t)cap * 27 * Cin);
+}
+static size_t rs_wgrad_bytes(int cap, int64_t Cin, int64_t Cout) {
+    return rs_al(4 * (size_t)cap * Cout) + rs_al(4 * 27 * (size_t)cap * Cin);
+}
+
+// the scan and the sparse data gradient's launches (gated on h[RS_SKIP_SPARSE]); um: the U region
+static void rs_dgrad_launch(const float* dz, const float* w, int64_t B, int H, int W, int D, int OD, int pz, int Cin,
+                            int Cout, float* dx, int accumulate, char* um, int cap, const RsHdr& hd, hipStream_t s) {
+    float* dzc = reinterpret_cast<float*>(um);
+    unsigned short* wp = reinterpret_cast<unsigned short*>(um + rs_al(4 * (size_t)cap * Cout));
+    float* ct = reinterpret_cast<float*>(um + rs_al(4 * (size_t)cap * Cout) + rs_al(6 * 27 * (size_t)Cin * Cout));
+    RsPack q{};
+    q.dzc = dzc; q.w = w; q.wp = wp; q.nw = (int64_t)27 * Cin * Cout;
+    rs_scan(dz, B * H * W * OD, Cout, cap, hd, q, s);
+    // ct[r][tap * Cin + c] = sum_n dzc[r][n] w[tap][c][n]: A = dzc (fp32), B = w as [27 Cin][Cout] planes
+    WinoWs g{};
+    g.U = dzc;
+    g.V = reinterpret_cast<float*>(wp);
+    g.M = ct;
+    wino_gemm_x3(g, cap, Cout, 27 * Cin, 1, s, true, hd.h + RS_SKIP_SPARSE, hd.h + RS_N);
+    const int64_t nvox = B * H * W * D;
+    hipLaunchKernelGGL(rs_dgrad_out_kernel, dim3((unsigned)((nvox + RS_VOX - 1) / RS_VOX)), dim3(256), 0, s, ct, nvox,
+                       H, W, D, OD, pz, Cin, accumulate, hd.h, hd.slot, dx);
+}
+
+// The unfused data gradient with every per-call choice as an argument: v_ready and tile_y as
+// m3d_conv3d_bwd_data_wino_vy, v (NULL, or the transformed weights of m3d_conv3d_wino_weight_v at this
+// tile_y, as m3d_conv3d_bwd_data_wino_xv) and rs_mode (RS_AUTO / RS_OFF / RS_ALWAYS above).
+extern "C" int m3d_conv3d_bwd_data_wino_rs(const float* dz, const float* w, int64_t B, int64_t H, int64_t W,
+                                           int64_t D, int64_t Cin, int64_t Cout, int64_t OD, int32_t pz, float* dx,
+                                           int32_t accumulate, void* workspace, size_t ws_bytes, int32_t v_ready,
+                                           int32_t tile_y, const void* v, int32_t rs_mode, m3d_stream_t s) {
+    int ny;
+    if (int rc = v ? wino_v_tile(1, tile_y, ny) : dgrad_tile_arg(tile_y, ny)) return rc;
+    if (rs_mode < RS_AUTO || rs_mode > RS_ALWAYS) return einval("conv3d winograd bwd-data: rs_mode must be 0, 1 or 2");
+    return bwd_data_wino(dz, w, B, H, W, D, Cin, Cout, OD, pz, dx, accumulate, workspace, ws_bytes, st(s), nullptr, 0,
+                         v_ready != 0, nullptr, ny, v, rs_mode);
+}
+
 // the data-gradient output transform: dx over the (halo-extended) grid, or,
 // for a depth slab with dx_halo, interior planes into dx (depth dl) and the
 // neighbours' planes into dx_halo [B][H][W][2][C]
@@ -5034,7 +5460,7 @@ static void bwd_data_wino_launch(const float* dz, const float* w, const WinoGeom
             hipLaunchKernelGGL((wino_input_kernel<NZ, false, false, NY>), igrid, dim3(256), 0, hs, dz, g, Cout, ws.U);
         else
             hipLaunchKernelGGL((wino_input_kernel<NZ, true, false, NY>), igrid, dim3(256), 0, hs, dz, g, Cout, ws.U);
-        wino_gemm_x3(ws, g.T, Cout, Cin, P, hs, af32);
+        wino_gemm_x3(ws, g.T, Cout, Cin, P, hs, af32, g.gate);
     } else {
         hipLaunchKernelGGL((wino_weight_kernel<NZ, false, NY>), wgrid, dim3(256), 0, hs, w, Cin, Cout, 1, ws.V);
         hipLaunchKernelGGL((wino_input_kernel<NZ, false, false, NY>), igrid, dim3(256), 0, hs, dz, g, Cout, ws.U);
@@ -5050,7 +5476,7 @@ static void bwd_data_wino_launch(const float* dz, const float* w, const WinoGeom
 static int bwd_data_wino(const float* dz, const float* w, int64_t B, int64_t H, int64_t W, int64_t D,
                          int64_t Cin, int64_t Cout, int64_t OD, int32_t pz, float* dx, int32_t accumulate,
                          void* workspace, size_t ws_bytes, hipStream_t hs, float* dx_halo, int hlo, bool v_ready,
-                         const Epi* fb, int ny_arg, const void* v_ext) {
+                         const Epi* fb, int ny_arg, const void* v_ext, int rs_mode) {
     int rc = wino_check(B, H, W, D, OD, pz, Cin, Cout);
     if (rc) return rc;
     if (wino_per_item(B, H, W, D, OD, Cin, Cout)) {
@@ -5059,23 +5485,37 @@ static int bwd_data_wino(const float* dz, const float* w, int64_t B, int64_t H, 
             rc = bwd_data_wino(dz + b * H * W * OD * Cout, w, 1, H, W, D, Cin, Cout, OD, pz, dx + b * H * W * dxd * Cin,
                                accumulate, workspace, ws_bytes, hs,
                                dx_halo ? dx_halo + b * H * W * 2 * Cin : nullptr, hlo, v_ready || b > 0, nullptr,
-                               ny_arg, v_ext);
+                               ny_arg, v_ext, RS_OFF);        // (the per-item loop stays dense)
             if (rc) return rc;
         }
         return M3D_OK;
     }
     const int nz = wino_dgrad_nz(), ny = ny_arg ? ny_arg : wino_dgrad_ny();
-    const WinoGeom g = wino_geom(B, H, W, D, OD, 2 - pz, nz, ny);
+    WinoGeom g = wino_geom(B, H, W, D, OD, 2 - pz, nz, ny);
     // the layout this call uses (its tile_y may differ from the library's default)
     if (ws_bytes < wino_ws_need(g, Cout, Cin, nz, ny))
         return einval("conv3d winograd: workspace too small");
     // same layout with the roles of Cin/Cout swapped (V'[P][Cout][Cin], U'[P][T][Cout])
     WinoWs ws = wino_ws(workspace, g, Cout, Cin, nz, ny);
+    float* const ws_u = ws.U;
     if (v_ext) {                        // transformed by m3d_conv3d_wino_weight_v (dgrad 1, this tile_y)
         ws.V = static_cast<float*>(const_cast<void*>(v_ext));
         v_ready = true;
     }
     const int ci = (int)Cin, co = (int)Cout, dl = (int)OD;
+    // row-sparse dz (the RPN head's gradient): scan, gate the launches below on the
+    // outcome and enqueue the sparse launches behind their own gate
+    const int64_t rows = B * H * W * OD;
+    const int cap = rs_cap(rows);
+    const size_t lay = wino_ws_layout(g, Cout, Cin, nz, ny);
+    const size_t um = lay - (size_t)(reinterpret_cast<char*>(ws_u) - static_cast<char*>(workspace));
+    if (!dx_halo && !fb && rs_attempt(rs_mode, rows, Cin, Cout) && rs_dgrad_bytes(cap, Cin, Cout) <= um &&
+        (int64_t)cap * 27 * Cin * 4 < 0xFFFFFFF0LL && 27 * Cin * Cout * 2 < 0xFFFFFFF0LL) {
+        const RsHdr hd = rs_hdr(static_cast<char*>(workspace) + lay, rows);
+        g.gate = hd.h + RS_SKIP_DENSE;
+        rs_dgrad_launch(dz, w, B, (int)H, (int)W, (int)D, (int)OD, pz, ci, co, dx, accumulate,
+                        reinterpret_cast<char*>(ws_u), cap, hd, hs);
+    }
     if (nz == 4 && ny == 4)
         bwd_data_wino_launch<4, 4>(dz, w, g, ws, ci, co, dx, accumulate, dx_halo, hlo, dl, v_ready, fb, hs);
     else if (nz == 4)
@@ -5090,7 +5530,7 @@ static int bwd_data_wino(const float* dz, const float* w, int64_t B, int64_t H, 
 static int bwd_weight_wino(const float* x, const float* u_in, const float* dz, int64_t B,
                            int64_t H, int64_t W, int64_t D, int64_t Cin, int64_t Cout, int64_t OD,
                            int32_t pz, float* dw, void* workspace, size_t ws_bytes, m3d_stream_t s,
-                           const float* halo = nullptr, int hlo = 0, int hhi = 0) {
+                           const float* halo = nullptr, int hlo = 0, int hhi = 0, int rs_mode = 0) {
     int rc = wino_check(B, H, W, D, OD, pz, Cin, Cout);
     if (rc) return rc;
     if (ws_bytes < m3d_conv3d_wino_workspace_bytes(B, H, W, D, OD, Cin, Cout))
@@ -5100,7 +5540,7 @@ static int bwd_weight_wino(const float* x, const float* u_in, const float* dz, i
         for (int64_t b = 0; b < B; ++b) {
             rc = bwd_weight_wino(x + b * H * W * D * Cin, nullptr, dz + b * H * W * OD * Cout, 1, H, W, D, Cin, Cout,
                                  OD, pz, dw, workspace, ws_bytes, s, halo ? halo + b * H * W * 2 * Cin : nullptr, hlo,
-                                 hhi);
+                                 hhi, RS_OFF);
             if (rc) return rc;
         }
         return M3D_OK;
@@ -5109,6 +5549,26 @@ static int bwd_weight_wino(const float* x, const float* u_in, const float* dz, i
     WinoGeom g = wino_geom(B, H, W, OD, D, pz, nz);
     g.halo = halo; g.hlo = hlo; g.hhi = hhi;
     WinoWs ws = wino_ws(workspace, g, Cin, Cout, nz);   // V <- dW_hat, U <- B^T x, M <- A dz
+    // row-sparse dz (see rs_scan): the launches below return when the scan finds dz
+    // sparse, and dw += xg[tap]^T dzc over the gathered active rows runs in their place
+    const int* gate = nullptr;
+    const int64_t rows = B * H * W * OD;
+    const int cap = rs_cap(rows);
+    const size_t lay = wino_ws_layout(g, Cin, Cout, nz, WNY);
+    const size_t um = lay - (size_t)(reinterpret_cast<char*>(ws.U) - static_cast<char*>(workspace));
+    if (x && !halo && wgrad_x3_env() && (Cout > 64 || Cin <= 64) && rs_attempt(rs_mode, rows, Cin, Cout) &&
+        rs_wgrad_bytes(cap, Cin, Cout) <= um) {
+        const RsHdr hd = rs_hdr(static_cast<char*>(workspace) + lay, rows);
+        gate = g.gate = hd.h + RS_SKIP_DENSE;
+        float* dzc = ws.U;
+        float* xg = reinterpret_cast<float*>(reinterpret_cast<char*>(ws.U) + rs_al(4 * (size_t)cap * Cout));
+        RsPack q{};
+        q.dzc = dzc; q.x = x; q.xg = xg;
+        q.H = (int)H; q.W = (int)W; q.D = (int)D; q.OD = (int)OD; q.pz = pz; q.Cx = (int)Cin;
+        rs_scan(dz, rows, (int)Cout, cap, hd, q, st(s));
+        launch_wgrad_x3(xg, dzc, dw, cap, (int)Cin, (int)Cout, 27, (int64_t)cap * Cin, 0, (int64_t)Cin * Cout, st(s),
+                        false, hd.h + RS_SKIP_SPARSE);
+    }
     // dW_hat is uninitialised scratch: the GEMM launcher stores into it where a
     // single workgroup owns each tile, and zero-fills it first where it accumulates
     if (u_in)
@@ -5122,7 +5582,7 @@ static int bwd_weight_wino(const float* x, const float* u_in, const float* dz, i
     int fe = 0;                 // the hipError_t of a failed zero-fill
     if (wgrad_x3_env() && (Cout > 64 || Cin <= 64)) {
         fe = launch_wgrad_x3(ws.U, ws.M, ws.V, g.T, (int)Cin, (int)Cout, wino_points(nz), g.T * Cin, g.T * Cout,
-                             (int64_t)Cin * Cout, st(s), true);
+                             (int64_t)Cin * Cout, st(s), true, gate);
     } else {
         ConvP p = wino_gemm_p(ws.U, g.T, (int)Cin, nullptr, (int)Cout);
         p.bsw = g.T * Cout;                 // dz (DY) batch stride
@@ -5135,7 +5595,7 @@ static int bwd_weight_wino(const float* x, const float* u_in, const float* dz, i
         return M3D_EHIP;
     }
     WINO_LAUNCH_NZ(nz, wino_wgrad_out_kernel, dim3(grid_for(Cin * Cout, 256)), dim3(256), 0, st(s),
-                       ws.V, (int)Cin, (int)Cout, dw);
+                       ws.V, (int)Cin, (int)Cout, dw, gate);
     return check_launch("conv3d winograd bwd-weight");
 }
 
@@ -5227,4 +5687,34 @@ extern "C" int m3d_conv3d_bwd_weight_wino_u(const float* u, const float* dz, int
     M3D_DET_SCOPE(det);
     if (!u) return einval("conv3d winograd: u must not be NULL");
     return bwd_weight_wino(nullptr, u, dz, B, H, W, D, Cin, Cout, OD, pz, dw, workspace, ws_bytes, s);
+}
+
+// Byte offset of the row-sparse header (m3d_conv3d_rowsparse_scan's layout) in the workspace of a
+// data-gradient call at tile_y (pass 0) or of a weight-gradient call (pass 1): for tests that read the
+// state a call decided on.  (size_t)-1 for invalid arguments or a batch past the 32-bit operand bound.
+extern "C" size_t m3d_conv3d_rowsparse_header_offset(int64_t B, int64_t H, int64_t W, int64_t D, int64_t OD,
+                                                     int32_t pz, int64_t Cin, int64_t Cout, int32_t pass,
+                                                     int32_t tile_y) {
+    if (wino_check(B, H, W, D, OD, pz, Cin, Cout) || wino_per_item(B, H, W, D, OD, Cin, Cout)) return (size_t)-1;
+    if (pass == 1) {
+        const int nz = wino_wgrad_nz();
+        return wino_ws_layout(wino_geom(B, H, W, OD, D, pz, nz), Cin, Cout, nz, WNY);
+    }
+    if (pass != 0 || (tile_y != 0 && tile_y != 2 && tile_y != 4)) return (size_t)-1;
+    const int nz = wino_dgrad_nz(), ny = tile_y ? tile_y : wino_dgrad_ny();
+    return wino_ws_layout(wino_geom(B, H, W, D, OD, 2 - pz, nz, ny), Cout, Cin, nz, ny);
+}
+
+// The kept-U form that also receives x [B,H,W,D,Cin]: the dense launches read u as
+// m3d_conv3d_bwd_weight_wino_u does (u NULL: they transform x, as m3d_conv3d_bwd_weight_wino), the
+// row-sparse path (rs_scan) gathers its rows from x.  rs_mode: RS_AUTO / RS_OFF / RS_ALWAYS.
+extern "C" int m3d_conv3d_bwd_weight_wino_ux(const float* u, const float* x, const float* dz, int64_t B, int64_t H,
+                                             int64_t W, int64_t D, int64_t Cin, int64_t Cout, int64_t OD,
+                                             int32_t pz, float* dw, void* workspace, size_t ws_bytes,
+                                             int32_t rs_mode, const m3d_det_t* det, m3d_stream_t s) {
+    M3D_DET_SCOPE(det);
+    if (!x) return einval("conv3d winograd: x must not be NULL");
+    if (rs_mode < RS_AUTO || rs_mode > RS_ALWAYS) return einval("conv3d winograd bwd-weight: rs_mode must be 0, 1 or 2");
+    return bwd_weight_wino(x, u, dz, B, H, W, D, Cin, Cout, OD, pz, dw, workspace, ws_bytes, s, nullptr, 0, 0,
+                           rs_mode);
 }

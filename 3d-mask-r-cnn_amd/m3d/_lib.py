@@ -142,6 +142,13 @@ _SIGS = {
                                  c_p, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_sz, c_p],
     "m3d_conv3d_bwd_weight_wino_u": [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,
                                      c_i32, c_p, c_p, c_sz, c_p, c_p],
+    "m3d_conv3d_bwd_weight_wino_ux": [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,
+                                      c_i32, c_p, c_p, c_sz, c_i32, c_p, c_p],
+    "m3d_conv3d_bwd_data_wino_rs": [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32,
+                                    c_p, c_i32, c_p, c_sz, c_i32, c_i32, c_p, c_i32, c_p],
+    "m3d_conv3d_rowsparse_scan_bytes": [c_i64],
+    "m3d_conv3d_rowsparse_header_offset": [c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i64, c_i64, c_i32, c_i32],
+    "m3d_conv3d_rowsparse_scan": [c_p, c_i64, c_i64, c_i32, c_p, c_sz, c_p],
     "m3d_gemm_f32_ex": [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p,
                         c_i32, c_i32, c_p],
     "m3d_splitk_reduce": [c_p, c_i32, c_i64, c_i64, c_p, c_p, c_p, c_i32, c_p, c_p],
@@ -242,6 +249,7 @@ _RESTYPES = {"m3d_last_error": ctypes.c_char_p, "m3d_nms3d_workspace_bytes": c_s
              "m3d_detection_targets_workspace_bytes": c_sz, "m3d_rpn_targets_workspace_bytes": c_sz,
              "m3d_rpn_loss_workspace_bytes": c_sz, "m3d_head_loss_workspace_bytes": c_sz,
              "m3d_bn_act_bwd_workspace_bytes": c_sz, "m3d_bn_bwd_fused_workspace_bytes": c_sz, "m3d_conv3d_splitk_count": c_i32, "m3d_conv3d_wino_workspace_bytes": c_sz, "m3d_conv3d_wino_dgrad_workspace_bytes": c_sz, "m3d_conv3d_wino_v_bytes": c_sz,
+             "m3d_conv3d_rowsparse_scan_bytes": c_sz, "m3d_conv3d_rowsparse_header_offset": c_sz,
              "m3d_conv3d_wino_u_bytes": c_sz, "m3d_conv3d_wino_tile_z": c_i32, "m3d_conv3d_wino_wgrad_tile_z": c_i32,
              "m3d_conv3d_wino_tile_y": c_i32, "m3d_conv3d_wino_dgrad_tile_y": c_i32,
              "m3d_conv3d_wino_dgrad_tile_z": c_i32, "m3d_col_sums_batched_workspace_bytes": c_sz,
@@ -279,7 +287,7 @@ def load(path: str = LIB_PATH):
 # target of this process's mode (set_deterministic) -- the mode is the host's
 # choice, kept here; libm3d itself holds none.
 DET_ENTRY_POINTS = ("m3d_conv3d_bwd_weight", "m3d_conv3d_bwd_weight_halo", "m3d_conv3d_bwd_weight_wino",
-                    "m3d_conv3d_bwd_weight_wino_u", "m3d_conv3d_bwd_weight_wino_halo", "m3d_gemm_wgrad_f32",
+                    "m3d_conv3d_bwd_weight_wino_u", "m3d_conv3d_bwd_weight_wino_ux", "m3d_conv3d_bwd_weight_wino_halo", "m3d_gemm_wgrad_f32",
                     "m3d_conv3d_bwd_weight_dil", "m3d_deconv3d_k2s2_bwd_weight",
                     "m3d_sgd_keras", "m3d_adam_keras", "m3d_adadelta_keras")
 

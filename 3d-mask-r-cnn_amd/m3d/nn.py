@@ -256,6 +256,13 @@ WINO_KEEP_MAX_BYTES = 8 * 2**30
 # largest Winograd workspace a shared kernel keeps across its calls
 SHARE_WINO_MAX_BYTES = 6 * 2**30
 
+# Row-sparse output gradients in the Winograd backward (the RPN head's dz holds
+# the sampled anchors' rows only; decided per call on the device):
+# the rs_mode of m3d_conv3d_bwd_data_wino_rs / m3d_conv3d_bwd_weight_wino_ux.
+# 0 the library's size threshold, 1 off (A/B: exactly the dense launches),
+# 2 attempt at every size (tests/test_gpu_rowsparse.py).
+ROWSPARSE = 0
+
 # Winograd F(4x2x4, 3^3) for stride-1 'same' 3x3x3 convs (False disables)
 WINOGRAD = True
 WINO_MIN_C = 64
@@ -1114,15 +1121,23 @@ def _wino_wgrad(ctx, x, dz, w, dw, side, direct):
             wsw, wswb = _wino_ws(B, H, W, dext, OD, Cin, Cout, x.device)
             if ctx.u is not None:
                 ctx.u.record_stream(torch.cuda.current_stream())
-                check(L.m3d_conv3d_bwd_weight_wino_u(ptr(ctx.u), ptr(dz), B, H, W, D, Cin, Cout, OD, geo.pad[2],
-                                                     ptr(dw), ptr(wsw), wswb, stream()), "conv3d_bwd_weight_wino_u")
+                if halo is None:
+                    # (x too: a row-sparse dz is reduced over its active rows, gathered from x)
+                    check(L.m3d_conv3d_bwd_weight_wino_ux(ptr(ctx.u), ptr(x), ptr(dz), B, H, W, D, Cin, Cout, OD,
+                                                          geo.pad[2], ptr(dw), ptr(wsw), wswb, ROWSPARSE, stream()),
+                          "conv3d_bwd_weight_wino_u")
+                else:       # a depth slab: x lacks the neighbours' planes that the kept U holds
+                    check(L.m3d_conv3d_bwd_weight_wino_u(ptr(ctx.u), ptr(dz), B, H, W, D, Cin, Cout, OD,
+                                                         geo.pad[2], ptr(dw), ptr(wsw), wswb, stream()),
+                          "conv3d_bwd_weight_wino_u")
             elif halo is not None:
                 check(L.m3d_conv3d_bwd_weight_wino_halo(ptr(x), ptr(halo[0]), halo[1], halo[2], ptr(dz), B, H, W, D,
                                                         Cin, Cout, ptr(dw), ptr(wsw), wswb, stream()),
                       "conv3d_bwd_weight_wino_halo")
             else:
-                check(L.m3d_conv3d_bwd_weight_wino(ptr(x), ptr(dz), B, H, W, D, Cin, Cout, OD, geo.pad[2],
-                                                   ptr(dw), ptr(wsw), wswb, stream()), "conv3d_bwd_weight_wino")
+                check(L.m3d_conv3d_bwd_weight_wino_ux(None, ptr(x), ptr(dz), B, H, W, D, Cin, Cout, OD, geo.pad[2],
+                                                      ptr(dw), ptr(wsw), wswb, ROWSPARSE, stream()),
+                      "conv3d_bwd_weight_wino")
         if LAYER_LOG is not None:
             exe = direct if small else \
                 _wino_exec(B, OH, OW, OD, Cin, Cout, int(L.m3d_conv3d_wino_wgrad_tile_z()))
@@ -1177,10 +1192,11 @@ def _wino_dgrad(ctx, x, dz, w, direct):
                     L.m3d_conv3d_bwd_data_wino_bny(*args, v_ready, d, bws, bwsb, ty, stream()),
                     "conv3d_bwd_data_wino_bn"))
         elif vd is not None:
-            check(L.m3d_conv3d_bwd_data_wino_xv(*args, ptr(vd[0]), ty, None, None, 0, stream()),
+            check(L.m3d_conv3d_bwd_data_wino_rs(*args, 0, ty, ptr(vd[0]), ROWSPARSE, stream()),
                   "conv3d_bwd_data_wino_xv")
         else:
-            check(L.m3d_conv3d_bwd_data_wino_vy(*args, v_ready, ty, stream()), "conv3d_bwd_data_wino")
+            check(L.m3d_conv3d_bwd_data_wino_rs(*args, v_ready, ty, None, ROWSPARSE, stream()),
+                  "conv3d_bwd_data_wino")
         _shared_wino_release(ctx.wshare)
     if LAYER_LOG is not None:
         _log("wino_dgrad", direct, _wino_exec(B, OH, OW, OD, Cin, Cout, int(L.m3d_conv3d_wino_dgrad_tile_z()),

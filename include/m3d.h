@@ -393,6 +393,40 @@ int m3d_conv3d_fwd_wino_keep(const float* x, int64_t B, int64_t H, int64_t W, in
 int m3d_conv3d_bwd_weight_wino_u(const float* u, const float* dz, int64_t B, int64_t H, int64_t W,
                                  int64_t D, int64_t Cin, int64_t Cout, int64_t OD, int32_t pz,
                                  float* dw, void* workspace, size_t ws_bytes, const m3d_det_t* det, m3d_stream_t s);
+/* The kept-U form that also receives x [B,H,W,D,Cin] (u NULL: the form of
+ * m3d_conv3d_bwd_weight_wino): the same result; a row-sparse dz (below) is
+ * reduced over its active rows, gathered from x.  rs_mode: below. */
+int m3d_conv3d_bwd_weight_wino_ux(const float* u, const float* x, const float* dz, int64_t B, int64_t H,
+                                  int64_t W, int64_t D, int64_t Cin, int64_t Cout, int64_t OD, int32_t pz,
+                                  float* dw, void* workspace, size_t ws_bytes, int32_t rs_mode,
+                                  const m3d_det_t* det, m3d_stream_t s);
+/* Row-sparse output gradients.  m3d_conv3d_bwd_data_wino(_v, _vy, _xv without
+ * bn) and m3d_conv3d_bwd_weight_wino(_ux) scan dz on the device and, when at
+ * most min(4096, rows / 32) of its voxel rows hold a non-zero, run a gather /
+ * GEMM / scatter over those rows in place of the Winograd launches (decided
+ * per call on the device: no host read-back, graph-replay safe).  rs_mode is
+ * a per-call test and A/B hook of the two entry points that take it (the
+ * library holds no mode; every other entry point runs 0): 0 attempt on large
+ * layers only, 1 never (exactly the dense launches), 2 attempt at every size.
+ * m3d_conv3d_bwd_data_wino_rs is the unfused data gradient with v_ready and
+ * tile_y as m3d_conv3d_bwd_data_wino_vy and v as m3d_conv3d_bwd_data_wino_xv
+ * (NULL: transform w into the workspace). */
+int m3d_conv3d_bwd_data_wino_rs(const float* dz, const float* w, int64_t B, int64_t H, int64_t W, int64_t D,
+                                int64_t Cin, int64_t Cout, int64_t OD, int32_t pz, float* dx, int32_t accumulate,
+                                void* workspace, size_t ws_bytes, int32_t v_ready, int32_t tile_y, const void* v,
+                                int32_t rs_mode, m3d_stream_t s);
+/* The scan alone (tests): ws (m3d_conv3d_rowsparse_scan_bytes(rows) bytes)
+ * receives int32 [64 + 4096] {state (1 dense, 2 sparse), skip_dense,
+ * skip_sparse, n, ...; at [64] the active rows ascending}, then the per-64-row
+ * counts [ceil(rows / 64)] and the row -> slot map [rows] (-1: inactive),
+ * each 256-byte aligned.  cap <= 4096: more active rows give state dense. */
+size_t m3d_conv3d_rowsparse_scan_bytes(int64_t rows);
+/* where that header lies in the workspace of a data-gradient call at tile_y
+ * (pass 0) or of a weight-gradient call (pass 1); (size_t)-1 if invalid */
+size_t m3d_conv3d_rowsparse_header_offset(int64_t B, int64_t H, int64_t W, int64_t D, int64_t OD, int32_t pz,
+                                          int64_t Cin, int64_t Cout, int32_t pass, int32_t tile_y);
+int m3d_conv3d_rowsparse_scan(const float* dz, int64_t rows, int64_t C, int32_t cap, void* ws, size_t ws_bytes,
+                              m3d_stream_t s);
 /* Depth-slab forms (multi-GPU sharding of one volume, m3d/slab.py): x is this
  * rank's slab [B,H,W,Dl,C] and x_halo [B,H,W,2,C] the neighbours' boundary
  * planes (plane 0 = z -1 from the lower rank, valid if has_lo; plane 1 = z Dl
