@@ -95,55 +95,33 @@ int rank_sort_u64(const uint64_t* u, const int64_t* pos, int64_t n, bool desc, b
 }  // namespace m3d
 
 // ---- tuning constants -------------------------------------------------------
-// Every kernel-variant choice of the product library is a compile-time constant
-// holding its measured-best value (DESIGN.md 5 lists the A/B runs).  An A/B
-// build overrides one:  make ab AB_DEFS=-DM3D_TUNE_ROI_SLICES=16  (libm3d_ab.so,
-// loaded with M3D_LIB_FILE=libm3d_ab.so).  Variants measured slower are compiled
-// only in such builds (if constexpr on these values).  The one runtime switch
-// left is M3D_OPERAND_LIMIT (conv3d.hip: lowers the 32-bit operand bound so the
-// per-batch-item path runs at test sizes; tests/test_gpu_conv.py).
-// GEMM forms on the exact bf16 split (bit mask, conv3d.hip x3_mask); 31 = all,
-// the implicit-GEMM convs included since round 4 (same-box step A/B with the
-// fused BN backward: 27.33 -> 27.08 ms, profiles/r04v_cx3_step_ab.txt)
-#ifndef M3D_TUNE_GEMM_X3
-#define M3D_TUNE_GEMM_X3 31
-#endif
+// The thresholds below are compile-time constants holding their measured-best
+// values (DESIGN.md 5 lists the A/B runs).  An A/B build overrides one:
+//   make ab AB_DEFS=-DM3D_TUNE_ROI_SLICES=16
+// (libm3d_ab.so, loaded with M3D_LIB_FILE=libm3d_ab.so).  They are thresholds
+// and counts only: conv3d.hip holds no switch between kernel forms -- every
+// settled form A/B was retired with its losing kernels, and the
+// library ships only kernels that an entry point can launch
+// (tests/test_convref.py).  The one runtime switch left is M3D_OPERAND_LIMIT
+// (conv3d.hip: lowers the 32-bit operand bound so the per-batch-item path runs
+// at test sizes; tests/test_gpu_conv.py).
+// fewest output rows reduced per workgroup of the split weight-gradient kernels
 #ifndef M3D_TUNE_WGRAD_MINM
 #define M3D_TUNE_WGRAD_MINM 512
 #endif
-#ifndef M3D_TUNE_X3W_TR
-#define M3D_TUNE_X3W_TR 1
-#endif
+// ... of the 256x256 x3_wgrad_tr_kernel
 #ifndef M3D_TUNE_X3W_TR_MINM
 #define M3D_TUNE_X3W_TR_MINM 256
 #endif
-// stream-K x3_wgrad_tr_kernel in non-deterministic mode (one balanced round
-// of workgroups instead of tiles x splits; 0: the split grid in both modes)
-#ifndef M3D_TUNE_X3W_SK
-#define M3D_TUNE_X3W_SK 1
-#endif
-// ... for weight-gradient GEMMs whose tiles have at least this many 16-row steps
+// stream-K x3_wgrad_tr_kernel (non-deterministic mode: one balanced round of
+// workgroups instead of tiles x splits) for weight-gradient GEMMs whose tiles
+// have at least this many 16-row steps
 #ifndef M3D_TUNE_X3W_SK_MIN_STEPS
 #define M3D_TUNE_X3W_SK_MIN_STEPS 32
 #endif
-// (Measured-slower variants and their switches were removed in round 6:
-// DESIGN.md section 8 lists them, docs/DESIGN_HISTORY.md has their numbers.)
-// Winograd output tile along y: F(2,3) (2) or F(4,3) (4), as NZ is along z.
-// 4 (round 4): 4x2x4 tiles, 144 points per 32 outputs instead of 96 per 16 --
-// 25 % fewer point-GEMM FLOPs and transform bytes; step 26.9 -> 25.0 ms at
-// 128^3 (same box, r04ny4_ab), parity suite green (profiles/r04ny4_parity_tests.log)
-#ifndef M3D_TUNE_WINO_NY
-#define M3D_TUNE_WINO_NY 4
-#endif
-#ifndef M3D_TUNE_WINO_NZ
-#define M3D_TUNE_WINO_NZ 4
-#endif
-#ifndef M3D_TUNE_WINO_WGRAD_NZ
-#define M3D_TUNE_WINO_WGRAD_NZ 4
-#endif
-// the data gradient's y tile (conv3d.hip wino_dgrad_ny): 2 = F(2x2x4) data
-// gradients beside F(4x2x4) forwards / weight gradients (round 5, accuracy);
-// 0 = the forward's
+// the Winograd data gradient's y tile (conv3d.hip wino_dgrad_ny): 2 = F(2x2x4)
+// data gradients beside F(4x2x4) forwards / weight gradients (round 5,
+// accuracy); 0 = the forward's
 #ifndef M3D_TUNE_WINO_DGRAD_NY
 #define M3D_TUNE_WINO_DGRAD_NY 2
 #endif

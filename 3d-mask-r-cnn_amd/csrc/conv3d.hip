@@ -1197,39 +1197,20 @@ static int num_cus() {
     return n;
 }
 
-// M3D_GEMM_X3 (bit mask, default 31): fp32 GEMMs on the exact 3-way bf16 split
-// (6 bf16 MFMAs per product, see split3) instead of v_mfma_f32_32x32x2_f32.
-// bit 0: Winograd fwd / bwd-data point GEMMs on operands pre-split by the
-// transforms (x3_gemm_kernel; measured 39.9 -> 37.9 ms/step at 128^3, GEMM
-// error vs fp64 below the f32 MFMA's: scripts/x3_accuracy.py); bit 1:
-// implicit-GEMM convs splitting in the LDS store (neutral to -0.3 ms/step
-// through round 3, on since round 4: -0.25 ms with the fused BN backward); bit 2: the
-// Winograd weight-gradient GEMMs (x3_wgrad_kernel; 38.2 -> 37.0 ms/step);
-// bit 3: the weight gradients of 1x1x1 stride-1 convs on the same kernel;
-// bit 4: the Winograd input transform writes U as fp32 (4 B per point
-// instead of 3 x 2 B) and the point GEMM (x3_gemm256_af_kernel, or
-// x3_gemm_kernel<AF32>) splits it on its way into LDS: a third less HBM
-// traffic for U, 34.2 -> 32.9 ms/step at 128^3 (default on).
-static int x3_mask() {
-    static constexpr int v = M3D_TUNE_GEMM_X3;
-    return v;
-}
-static int gemm_x3_env() { return x3_mask() & 1; }
-static int conv_x3_env() { return (x3_mask() >> 1) & 1; }
-
+// Every fp32 GEMM that has a form on the exact 3-way bf16 split (6 bf16 MFMAs
+// per product, see split3) runs it instead of v_mfma_f32_32x32x2_f32: the
+// Winograd point GEMMs (x3_gemm256_af_kernel / x3_gemm_kernel<AF32>: the input
+// transform writes U as fp32 and the GEMM splits it on its way into LDS), the
+// vector-loader implicit-GEMM convs (X3: split in the LDS store), the Winograd
+// and 1x1x1 weight gradients (x3_wgrad*_kernel).  DESIGN.md 8 lists the f32
+// forms these replaced and their A/B runs.
 template <int BM, int BN, int WM, int WN, bool BT, bool AVEC, int BK>
 static void launch_gemm(const ConvP& p, const Epi& e, hipStream_t s, int nbatch) {
     dim3 grid((unsigned)((p.M + BM - 1) / BM), (unsigned)((p.N + BN - 1) / BN), (unsigned)nbatch);
     if constexpr (BT && BK == 32) {
         if (e.fbn) {                       // the fused BN-ReLU backward's own instantiation
-            if constexpr (AVEC) {
-                if (conv_x3_env()) {       // the same GEMM form as the unfused data gradient
-                    hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, BT, AVEC, BK, 1, false, true, true>), grid,
-                                       dim3(256), 0, s, p, e);
-                    return;
-                }
-            }
-            hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, BT, AVEC, BK, 1, false, false, true>), grid,
+            // (vector loader: the same GEMM form as the unfused data gradient)
+            hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, BT, AVEC, BK, 1, false, AVEC, true>), grid,
                                dim3(256), 0, s, p, e);
             return;
         }
@@ -1245,25 +1226,16 @@ static void launch_gemm(const ConvP& p, const Epi& e, hipStream_t s, int nbatch)
         ConvP pp = p;
         pp.nbatch = nbatch;
         const unsigned g = (unsigned)(resident / 8 * 8);
-        if constexpr (BT || BN >= 64) {
-            if (conv_x3_env()) {
-                if (persist)
-                    hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, BT, AVEC, BK, 1, true, true>), dim3(g),
-                                       dim3(256), 0, s, pp, e);
-                else
-                    hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, BT, AVEC, BK, 1, false, true>), grid,
-                                       dim3(256), 0, s, p, e);
-                return;
-            }
-        }
+        constexpr bool X3 = BT || BN >= 64;  // (the 128x32 forward tile has no split form)
         if (persist)
-            hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, BT, AVEC, BK, 1, true>), dim3(g), dim3(256), 0, s,
-                               pp, e);
+            hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, BT, AVEC, BK, 1, true, X3>), dim3(g), dim3(256), 0,
+                               s, pp, e);
         else
-            hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, BT, AVEC, BK, 1>), grid, dim3(256), 0, s, p, e);
-        return;
+            hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, BT, AVEC, BK, 1, false, X3>), grid, dim3(256), 0, s,
+                               p, e);
+    } else {
+        hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, BT, AVEC, BK, 2>), grid, dim3(256), 0, s, p, e);
     }
-    hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, BT, AVEC, BK, 2>), grid, dim3(256), 0, s, p, e);
 }
 
 template <bool BT, bool AVEC>
@@ -1802,19 +1774,13 @@ __global__ __launch_bounds__(512, 1) void x3_wgrad_tr_kernel(const float* __rest
     x3w_segment<DBG>(smem, A + batch * bsa, Bm + batch * bsb, C + batch * bsc, M, K, N, ms, me, k0, n0, wo, wp, bz);
 }
 
-// M3D_X3W_TR (default 1): the 256x256 transposed-read weight-gradient kernel
-// for GEMMs with K, N >= 192; 0 keeps the 128x128 x3_wgrad_kernel everywhere.
-static int wgrad_tr_env() {
-    static constexpr int v = M3D_TUNE_X3W_TR;
-    return v;
-}
-
+// The 256x256 transposed-read weight-gradient kernel, for GEMMs with K, N >= 192
 static int launch_wgrad_tr(const float* A, const float* Bm, float* C, int64_t M, int K, int N, int nbatch,
                            int64_t bsa, int64_t bsb, int64_t bsc, hipStream_t s, bool fresh, const int* gate) {
     const int64_t tiles = (int64_t)((K + 255) / 256) * ((N + 255) / 256) * nbatch;
     const int64_t cus = num_cus();
     static constexpr int64_t minm = M3D_TUNE_X3W_TR_MINM;
-    if (M3D_TUNE_X3W_SK && !det().on && M >= (int64_t)M3D_TUNE_X3W_SK_MIN_STEPS * W2_BK) {
+    if (!det().on && M >= (int64_t)M3D_TUNE_X3W_SK_MIN_STEPS * W2_BK) {
         // stream-K (X3wSK): one balanced round of workgroups, each >= minm rows
         // (only for tiles of >= 32 steps: with short tiles the minm floor would
         // give one workgroup a run of tiles, each with its own atomic epilogue)
@@ -1861,9 +1827,6 @@ static int launch_wgrad_tr(const float* A, const float* Bm, float* C, int64_t M,
     return 0;
 }
 
-// M3D_GEMM_X3 bit 2: the batched Winograd weight-gradient GEMMs on x3_wgrad_kernel
-static int wgrad_x3_env() { return (x3_mask() >> 2) & 1; }
-
 // C[b] += A[b]^T B[b]: A [M][K], B [M][N], C [K][N], batch strides bsa/bsb/bsc.
 // fresh: C is uninitialised scratch (nbatch contiguous items, bsc = K * N) and
 // the result is C[b] = A[b]^T B[b]: owner store or zero-fill, see wg_settle.
@@ -1871,7 +1834,7 @@ static int wgrad_x3_env() { return (x3_mask() >> 2) & 1; }
 static int launch_wgrad_x3(const float* A, const float* Bm, float* C, int64_t M, int K, int N, int nbatch,
                            int64_t bsa, int64_t bsb, int64_t bsc, hipStream_t s, bool fresh = false,
                            const int* gate = nullptr) {
-    if (wgrad_tr_env() && K >= 192 && N >= 192)
+    if (K >= 192 && N >= 192)
         return launch_wgrad_tr(A, Bm, C, M, K, N, nbatch, bsa, bsb, bsc, s, fresh, gate);
     if (K <= 64 || N <= 64) {          // x3_wgrad64_kernel: 64x64 tiles, the m chunk over the waves
         const int64_t tiles = (int64_t)((K + 63) / 64) * ((N + 63) / 64);
@@ -1914,9 +1877,10 @@ static int launch_wgrad_x3(const float* A, const float* Bm, float* C, int64_t M,
 
 // =========================================================================
 // Winograd F(NYx2xNZ, 3x3x3) for stride-1 'same' 3x3x3 convs: F(NY,3) along y
-// (NY = M3D_TUNE_WINO_NY: 4 by default since round 4, 2), F(2,3) along x,
-// F(NZ,3) along z (NZ = 2, or 4 by default).  The F(2,3) formulas below are
-// written for y and x; with NY = 4 the y axis takes the F(4,3) ones (ZT<4>).
+// (NY = 4; the data gradient also has NY = 2), F(2,3) along x, F(NZ,3) along z
+// (every launch uses NZ = 4; the kernels keep the parameter).  The F(2,3)
+// formulas below are written for y and x; with NY = 4 the y axis takes the
+// F(4,3) ones (ZT<4>).
 //   fwd:   Y   = A^T [ (G W G^T) . (B^T X B) ] A        (per 2x2xNZ output tile)
 //   dgrad: dX  = same with W'[t][n][c] = W[flip t][c][n]
 //   wgrad: dW  = G^T [ sum_tiles (B^T X B) . (A dZ A^T) ] G
@@ -2059,10 +2023,10 @@ template <> struct ZT<4> {
     }
 };
 
-// y-axis transforms: F(WNY,3) -- 2: F(2,3) as on x; 4: F(4,3) as on z (a 4x2xNZ
-// output tile: 4.5 instead of 6 points per output for NZ = 4, at a larger
-// rounding amplification; M3D_TUNE_WINO_NY)
-constexpr int WNY = M3D_TUNE_WINO_NY;
+// y-axis transforms of the forward and the weight gradient: F(4,3) as on z (a
+// 4x2x4 output tile: 4.5 instead of 6 points per output, at a larger rounding
+// amplification).  The data gradient's y tile is NYT = 2 or 4 (tile_y).
+constexpr int WNY = 4;
 using YT = ZT<WNY>;
 constexpr int PY = YT::P;
 
@@ -3287,26 +3251,16 @@ __global__ __launch_bounds__(512, 1) void x3_gemm256_af_kernel(X3G g) {
 }
 
 
-// M3D_WINO_NZ = 2 selects the F(2x2x2) tiles (A/B testing; default 4: F(2x2x4))
-static int wino_nz() {
-    static constexpr int v = M3D_TUNE_WINO_NZ;
-    return v;
-}
-// The weight gradient runs on the forward's F(2x2x4) tiles (round 3; was
-// F(2x2x2)): the forward keeps its fp32 transformed input U and the weight
-// gradient reads it (no second input transform), with 96 instead of 64 point
-// GEMMs over half the tiles -- 25 % fewer MFMA FLOPs.  Its tile-summed products
-// pass through G^T, whose F(4,3) rows amplify the fp32 summation error:
-// measured 3.3e-6 / 2.8e-6 vs F(2x2x2)'s 1.0e-6 / 1.2e-6 of the gradient's
-// scale (128 -> 128 / 256 -> 512 convs, test_wino_weight_gradient_accuracy),
-// whole-step gradients at 128^3 median 1.2e-6 vs float64; step 30.9 -> 29.7 ms.
-// M3D_WINO_WGRAD_NZ=2 restores F(2x2x2).
-static int wino_wgrad_nz() {
-    static constexpr int v = M3D_TUNE_WINO_WGRAD_NZ;
-    return v;
-}
-// the data gradient's z tile: the forward's
-static int wino_dgrad_nz() { return wino_nz(); }
+// The z tile of every pass: F(4,3).  The weight gradient runs on the forward's
+// tiles (round 3; was F(2x2x2)): the forward keeps its fp32 transformed input U
+// and the weight gradient reads it (no second input transform), with 96
+// instead of 64 point GEMMs over half the tiles -- 25 % fewer MFMA FLOPs.  Its
+// tile-summed products pass through G^T, whose F(4,3) rows amplify the fp32
+// summation error: measured 3.3e-6 / 2.8e-6 vs F(2x2x2)'s 1.0e-6 / 1.2e-6 of
+// the gradient's scale (128 -> 128 / 256 -> 512 convs,
+// test_wino_weight_gradient_accuracy), whole-step gradients at 128^3 median
+// 1.2e-6 vs float64; step 30.9 -> 29.7 ms.
+constexpr int WNZ = 4;
 // The data gradient's y tile (round 5): F(2,3) along y by default, i.e.
 // F(2x2x4) tiles, while the forward and the weight gradient keep F(4x2x4).
 // The data gradients carry the step's gradient error (every layer's dx feeds
@@ -3319,15 +3273,12 @@ static int wino_dgrad_ny() {
     static constexpr int v = M3D_TUNE_WINO_DGRAD_NY;
     return v ? v : WNY;
 }
-static int wino_points(int nz, int ny = WNY) { return (ny + 2) * 4 * (nz + 2); }
-static int wino_points() { return wino_points(wino_nz()); }
+static int wino_points(int ny = WNY) { return (ny + 2) * 4 * (WNZ + 2); }
 
-static WinoGeom wino_geom(int64_t B, int64_t H, int64_t W, int64_t D, int64_t Din, int pz,
-                          int nz = -1, int ny = WNY) {
+static WinoGeom wino_geom(int64_t B, int64_t H, int64_t W, int64_t D, int64_t Din, int pz, int ny = WNY) {
     WinoGeom g{};
-    if (nz < 0) nz = wino_nz();
     g.B = (int)B; g.H = (int)H; g.W = (int)W; g.D = (int)D; g.Din = (int)Din; g.pz = pz;
-    g.TY = (int)((H + ny - 1) / ny); g.TX = (int)((W + 1) / 2); g.TZ = (int)((D + nz - 1) / nz);
+    g.TY = (int)((H + ny - 1) / ny); g.TX = (int)((W + 1) / 2); g.TZ = (int)((D + WNZ - 1) / WNZ);
     g.T = B * g.TY * g.TX * g.TZ;
     g.halo = nullptr;
     g.hlo = g.hhi = 0;
@@ -3383,15 +3334,14 @@ extern "C" int m3d_gemm_wgrad_f32(const float* A, const float* Bm, float* C, int
     const int64_t lim = (int64_t)0xFFFFFFF0 / 4;
     if (M >= 0x7FFFFFFF || M * K >= lim || M * N >= lim || K * N >= lim)
         return einval("gemm_wgrad: operand larger than 4 GiB (32-bit buffer offsets)");
-    if (wgrad_x3_env() && N > 64) {
+    if (N > 64) {
         launch_wgrad_x3(A, Bm, C, M, (int)K, (int)N, (int)batch, M * K, M * N, K * N, st(s));
         return check_launch("m3d_gemm_wgrad_f32 (x3)");
     }
     ConvP p = wino_gemm_p(A, M, (int)K, nullptr, (int)N);
     p.bsw = M * N;                      // B batch stride
     p.bsy = K * N;                      // C batch stride
-    if (N <= 64) launch_wgrad<128, 64, 2, 2, true>(p, Bm, C, st(s), (int)batch);
-    else launch_wgrad<128, 128, 2, 2, true>(p, Bm, C, st(s), (int)batch);
+    launch_wgrad<128, 64, 2, 2, true>(p, Bm, C, st(s), (int)batch);
     return check_launch("m3d_gemm_wgrad_f32");
 }
 
@@ -4233,7 +4183,7 @@ extern "C" int m3d_conv3d_bwd_weight_dil(const float* x, const float* dz, int64_
     // dW += x^T dz -- on the exact bf16 split like the Winograd ones
     // M3D_WGRAD1_X3_MIN_N: smallest Cout taking this path (A/B: 65 = round 2's Cout > 64)
     static constexpr int min_n = M3D_TUNE_WGRAD1_X3_MIN_N;
-    if (vec && ((x3_mask() >> 3) & 1) && kh == 1 && kw == 1 && kd == 1 && sy == 1 && sx == 1 && sz == 1 &&
+    if (vec && kh == 1 && kw == 1 && kd == 1 && sy == 1 && sx == 1 && sz == 1 &&
         py == 0 && px == 0 && pz == 0 && OH == H && OW == W && OD == D && Cout >= min_n) {
         launch_wgrad_x3(x, dz, dw, p.M, (int)Cin, (int)Cout, 1, 0, 0, 0, st(s));
         return check_launch("x3_wgrad_kernel (1x1x1)");
@@ -4387,19 +4337,14 @@ static bool wino_per_item(int64_t B, int64_t H, int64_t W, int64_t D, int64_t OD
 // Workspace: V [P][Cin][Cout] + U [P][T][C1] + M [P][T][C2] (P = 16*(NZ+2) points) with
 // {C1, C2} = {Cin, Cout} (fwd / wgrad) or {Cout, Cin} (bwd-data), T the larger
 // of the fwd (tiles over OD) and bwd-data (tiles over D) tile counts.
-// launch the F(2x2xNZ) instantiation of a Winograd transform kernel
-#define WINO_LAUNCH_NZ(nz, kern, ...)                                            \
-    do {                                                                         \
-        if ((nz) == 4) hipLaunchKernelGGL(kern<4>, __VA_ARGS__);                 \
-        else hipLaunchKernelGGL(kern<2>, __VA_ARGS__);                           \
-    } while (0)
-#define WINO_LAUNCH(kern, ...) WINO_LAUNCH_NZ(wino_nz(), kern, __VA_ARGS__)
+// launch the NZ = 4 instantiation of a Winograd transform kernel
+#define WINO_LAUNCH(kern, ...) hipLaunchKernelGGL(kern<WNZ>, __VA_ARGS__)
 
-extern "C" int32_t m3d_conv3d_wino_tile_z(void) { return wino_nz(); }
-extern "C" int32_t m3d_conv3d_wino_wgrad_tile_z(void) { return wino_wgrad_nz(); }
+extern "C" int32_t m3d_conv3d_wino_tile_z(void) { return WNZ; }
+extern "C" int32_t m3d_conv3d_wino_wgrad_tile_z(void) { return WNZ; }
 extern "C" int32_t m3d_conv3d_wino_tile_y(void) { return WNY; }
 extern "C" int32_t m3d_conv3d_wino_dgrad_tile_y(void) { return wino_dgrad_ny(); }
-extern "C" int32_t m3d_conv3d_wino_dgrad_tile_z(void) { return wino_dgrad_nz(); }
+extern "C" int32_t m3d_conv3d_wino_dgrad_tile_z(void) { return WNZ; }
 
 // the row-sparse header behind a call's layout (rs_hdr, below) for dz of `rows` voxel rows
 static size_t rs_hdr_bytes(int64_t rows);
@@ -4410,13 +4355,11 @@ extern "C" size_t m3d_conv3d_wino_workspace_bytes(int64_t B, int64_t H, int64_t 
     if (wino_per_item(B, H, W, D, OD, Cin, Cout)) B = 1;     // run one batch item at a time
     size_t best = 0;
     // the data gradient's y tile is a per-call argument (m3d_conv3d_bwd_data_wino_vy / _bny): both sizes
-    const int tiles[4][2] = {{wino_nz(), WNY}, {wino_wgrad_nz(), WNY}, {wino_dgrad_nz(), 2}, {wino_dgrad_nz(), 4}};
-    for (const auto& zy : tiles) {
-        const int nz = zy[0], ny = zy[1];
-        const WinoGeom g = wino_geom(B, H, W, D > OD ? D : OD, D, 1, nz, ny);
-        const size_t P = (size_t)wino_points(nz, ny);
-        const size_t eb = gemm_x3_env() ? 6 : 4;      // X3: V and U hold three bf16 planes
-        const size_t wt = gemm_x3_env() ? al(sizeof(float) * 27 * (size_t)Cin * Cout) : 0;
+    for (const int ny : {2, 4}) {
+        const WinoGeom g = wino_geom(B, H, W, D > OD ? D : OD, D, 1, ny);
+        const size_t P = (size_t)wino_points(ny);
+        const size_t eb = 6;                          // V holds three bf16 planes; U is laid out alike
+        const size_t wt = al(sizeof(float) * 27 * (size_t)Cin * Cout);
         // U (eb bytes / element) then M (fp32), in either role order (fwd: U over
         // Cin, M over Cout; bwd-data: the reverse)
         const size_t um1 = al(eb * P * (size_t)g.T * Cin) + al(4 * P * (size_t)g.T * Cout);
@@ -4428,18 +4371,18 @@ extern "C" size_t m3d_conv3d_wino_workspace_bytes(int64_t B, int64_t H, int64_t 
 }
 
 struct WinoWs { float *V, *U, *M, *WT; };
-// bytes wino_ws lays out for geometry g, operand widths C1 (U) / C2 (M) and the tile (nz, ny);
+// bytes wino_ws lays out for geometry g, operand widths C1 (U) / C2 (M) and the y tile;
 // the row-sparse header follows at this offset
-static size_t wino_ws_layout(const WinoGeom& g, int64_t C1, int64_t C2, int nz, int ny) {
+static size_t wino_ws_layout(const WinoGeom& g, int64_t C1, int64_t C2, int ny) {
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t P = (size_t)wino_points(nz, ny);
-    const size_t eb = gemm_x3_env() ? 6 : 4;
-    const size_t wt = gemm_x3_env() ? al(sizeof(float) * 27 * (size_t)C1 * C2) : 0;
+    const size_t P = (size_t)wino_points(ny);
+    const size_t eb = 6;
+    const size_t wt = al(sizeof(float) * 27 * (size_t)C1 * C2);
     return wt + al(eb * P * (size_t)C1 * C2) + al(eb * P * (size_t)g.T * C1) + al(4 * P * (size_t)g.T * C2);
 }
 // what a data-gradient call checks: its layout and the header for dz rows of depth max(D, OD)
-static size_t wino_ws_need(const WinoGeom& g, int64_t C1, int64_t C2, int nz, int ny) {
-    return wino_ws_layout(g, C1, C2, nz, ny) + rs_hdr_bytes((int64_t)g.B * g.H * g.W * (g.D > g.Din ? g.D : g.Din));
+static size_t wino_ws_need(const WinoGeom& g, int64_t C1, int64_t C2, int ny) {
+    return wino_ws_layout(g, C1, C2, ny) + rs_hdr_bytes((int64_t)g.B * g.H * g.W * (g.D > g.Din ? g.D : g.Din));
 }
 // the data gradient's own workspace at tile_y (0: the library default): the
 // layout bwd_data_wino checks (dz transformed over Cout, dx's points over Cin)
@@ -4447,47 +4390,29 @@ extern "C" size_t m3d_conv3d_wino_dgrad_workspace_bytes(int64_t B, int64_t H, in
                                                         int64_t Cin, int64_t Cout, int32_t tile_y) {
     if (tile_y != 0 && tile_y != 2 && tile_y != 4) return 0;
     if (wino_per_item(B, H, W, D, OD, Cin, Cout)) B = 1;
-    const int nz = wino_dgrad_nz(), ny = tile_y ? tile_y : wino_dgrad_ny();
-    return wino_ws_need(wino_geom(B, H, W, D, OD, 1, nz, ny), Cout, Cin, nz, ny);
+    const int ny = tile_y ? tile_y : wino_dgrad_ny();
+    return wino_ws_need(wino_geom(B, H, W, D, OD, 1, ny), Cout, Cin, ny);
 }
-// [WT: X3 only, the transposed kernel][V][U][M]
-static WinoWs wino_ws(void* ws, const WinoGeom& g, int64_t Cin, int64_t Cout, int nz = -1, int ny = WNY) {
+// [WT: the transposed kernel][V][U][M]
+static WinoWs wino_ws(void* ws, const WinoGeom& g, int64_t Cin, int64_t Cout, int ny = WNY) {
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t P = (size_t)wino_points(nz < 0 ? wino_nz() : nz, ny);
+    const size_t P = (size_t)wino_points(ny);
     char* p = (char*)ws;
     WinoWs w{};
-    w.WT = (float*)p;
-    if (gemm_x3_env()) p += al(sizeof(float) * 27 * (size_t)Cin * Cout);
-    const size_t eb = gemm_x3_env() ? 6 : 4;
+    w.WT = (float*)p; p += al(sizeof(float) * 27 * (size_t)Cin * Cout);
+    const size_t eb = 6;
     w.V = (float*)p; p += al(eb * P * (size_t)Cin * Cout);
     w.U = (float*)p; p += al(eb * P * (size_t)g.T * Cin);
     w.M = (float*)p;
     return w;
 }
 
-#define WINO_LAUNCH_NZ_X3(nz, kern, ...)                                         \
-    do {                                                                         \
-        if ((nz) == 4) hipLaunchKernelGGL((kern<4, true>), __VA_ARGS__);         \
-        else hipLaunchKernelGGL((kern<2, true>), __VA_ARGS__);                   \
-    } while (0)
-// the input transform, reading a depth slab's halo planes when g.halo is set
-#define WINO_INPUT(nz, x3o, grid, s, x, g, C, U)                                                          \
+// the input transform (U in fp32), reading a depth slab's halo planes when g.halo is set
+#define WINO_INPUT(grid, s, x, g, C, U)                                                                    \
     do {                                                                                                   \
-        const bool h_ = (g).halo != nullptr;                                                               \
-        if ((nz) == 4) {                                                                                   \
-            if (x3o) { if (h_) hipLaunchKernelGGL((wino_input_kernel<4, true, true>), grid, dim3(256), 0, s, x, g, C, U); \
-                       else hipLaunchKernelGGL((wino_input_kernel<4, true, false>), grid, dim3(256), 0, s, x, g, C, U); } \
-            else { if (h_) hipLaunchKernelGGL((wino_input_kernel<4, false, true>), grid, dim3(256), 0, s, x, g, C, U); \
-                   else hipLaunchKernelGGL((wino_input_kernel<4, false, false>), grid, dim3(256), 0, s, x, g, C, U); } \
-        } else {                                                                                           \
-            if (x3o) { if (h_) hipLaunchKernelGGL((wino_input_kernel<2, true, true>), grid, dim3(256), 0, s, x, g, C, U); \
-                       else hipLaunchKernelGGL((wino_input_kernel<2, true, false>), grid, dim3(256), 0, s, x, g, C, U); } \
-            else { if (h_) hipLaunchKernelGGL((wino_input_kernel<2, false, true>), grid, dim3(256), 0, s, x, g, C, U); \
-                   else hipLaunchKernelGGL((wino_input_kernel<2, false, false>), grid, dim3(256), 0, s, x, g, C, U); } \
-        }                                                                                                  \
+        if ((g).halo) hipLaunchKernelGGL((wino_input_kernel<WNZ, false, true>), grid, dim3(256), 0, s, x, g, C, U); \
+        else hipLaunchKernelGGL((wino_input_kernel<WNZ, false, false>), grid, dim3(256), 0, s, x, g, C, U); \
     } while (0)
-
-static int x3_af32_env() { return (x3_mask() >> 4) & 1; }
 
 // the P point GEMMs M[xi] = U[xi] V[xi] on split planes (U: T x K, V: N x K);
 // af32: U is fp32 [P][T][K] (split in the GEMM's LDS store)
@@ -4750,8 +4675,6 @@ extern "C" int m3d_conv3d_bwd_data_x3_bna(const float* dz, const uint16_t* plane
 }
 
 extern "C" size_t m3d_conv3d_wino_u_bytes(int64_t B, int64_t H, int64_t W, int64_t OD, int64_t Cin) {
-    if (wino_nz() != wino_wgrad_nz()) return 0;       // forward tiles differ from the wgrad's: nothing to keep
-    if (gemm_x3_env() && !x3_af32_env()) return 0;     // the forward's U is in bf16 planes
     return sizeof(float) * wino_points() * (size_t)wino_geom(B, H, W, OD, OD, 1).T * (size_t)Cin;
 }
 
@@ -4790,52 +4713,26 @@ static int fwd_wino(const float* x, int64_t B, int64_t H, int64_t W, int64_t D, 
         gi.tz_mode = 1; gi.halo = nullptr; gi.hlo = gi.hhi = 0;
         ge.tz_mode = 2;
     }
-    if (gemm_x3_env() && (!u_keep || x3_af32_env())) {
-        // (the fp32-A GEMM reads U in fp32: a kept U is written in place for the weight gradient)
-        if (u_keep) ws.U = u_keep;
-        if (v_ext) ws.V = static_cast<float*>(const_cast<void*>(v_ext));   // transformed by m3d_conv3d_wino_weight_v
-        float* wt = ws.WT;
-        if (!v_ready && !v_ext && phase != 2) {   // v_ready: V already holds this w's transform (an earlier call, same workspace)
-            hipLaunchKernelGGL(x3_wt_kernel, dim3((unsigned)((Cout + 31) / 32), (unsigned)((Cin + 31) / 32), 27),
-                               dim3(256), 0, s, w, (int)Cin, (int)Cout, wt);
-            WINO_LAUNCH_NZ_X3(wino_nz(), wino_weight_kernel, dim3(grid_for(Cin * Cout, 256)), dim3(256), 0, s, wt,
-                              (int)Cin, (int)Cout, 0, ws.V);
-        }
-        const bool af32 = x3_af32_env();
-        if (phase == 1) {
-            WINO_INPUT(wino_nz(), !af32, dim3(grid_for(g.T * Cin, 256)), s, x, gi, (int)Cin, ws.U);
-            return check_launch("conv3d winograd fwd (x3, phase 1)");
-        }
-        if (phase == 2) WINO_INPUT(wino_nz(), !af32, dim3(grid_for(g.T * Cin, 256)), s, x, ge, (int)Cin, ws.U);
-        else WINO_INPUT(wino_nz(), !af32, dim3(grid_for(g.T * Cin, 256)), s, x, g, (int)Cin, ws.U);
-        wino_gemm_x3(ws, g.T, (int)Cin, (int)Cout, wino_points(), s, af32);
-        Epi o{};
-        o.bias = bias; o.scale = bn_scale; o.shift = bn_shift; o.res = residual;
-        o.res_mode = residual ? 1 : 0; o.relu = relu; o.z = z_out; o.y = y; o.ldy = Cout;
-        WINO_LAUNCH(wino_output_kernel, dim3(grid_for(g.T * Cout, 256)), dim3(256), 0, s, ws.M,
-                    g, (int)Cout, o);
-        return check_launch("conv3d winograd fwd (x3)");
-    }
+    // (the fp32-A GEMM reads U in fp32: a kept U is written in place for the weight gradient)
     if (u_keep) ws.U = u_keep;
-    if (phase != 2)
-        WINO_LAUNCH(wino_weight_kernel, dim3(grid_for(Cin * Cout, 256)), dim3(256), 0, s, w,
+    if (v_ext) ws.V = static_cast<float*>(const_cast<void*>(v_ext));   // transformed by m3d_conv3d_wino_weight_v
+    if (!v_ready && !v_ext && phase != 2) {   // v_ready: V already holds this w's transform (an earlier call, same workspace)
+        hipLaunchKernelGGL(x3_wt_kernel, dim3((unsigned)((Cout + 31) / 32), (unsigned)((Cin + 31) / 32), 27),
+                           dim3(256), 0, s, w, (int)Cin, (int)Cout, ws.WT);
+        hipLaunchKernelGGL((wino_weight_kernel<WNZ, true>), dim3(grid_for(Cin * Cout, 256)), dim3(256), 0, s, ws.WT,
                            (int)Cin, (int)Cout, 0, ws.V);
-    if (phase == 1) {
-        WINO_INPUT(wino_nz(), false, dim3(grid_for(g.T * Cin, 256)), s, x, gi, (int)Cin, ws.U);
-        return check_launch("conv3d winograd fwd (phase 1)");
     }
-    WINO_INPUT(wino_nz(), false, dim3(grid_for(g.T * Cin, 256)), s, x, phase == 2 ? ge : g, (int)Cin, ws.U);
-    ConvP p = wino_gemm_p(ws.U, g.T, (int)Cin, ws.V, (int)Cout);
-    Epi e{};
-    e.y = ws.M; e.ldy = Cout; e.simple = 1; e.YH = 1; e.YW = 1; e.YD = (int)g.T;
-    e.ysy = e.ysx = e.ysz = 1;
-    dispatch_gemm<false, true>(p, e, s, wino_points());
+    if (phase == 1) {
+        WINO_INPUT(dim3(grid_for(g.T * Cin, 256)), s, x, gi, (int)Cin, ws.U);
+        return check_launch("conv3d winograd fwd (x3, phase 1)");
+    }
+    WINO_INPUT(dim3(grid_for(g.T * Cin, 256)), s, x, phase == 2 ? ge : g, (int)Cin, ws.U);
+    wino_gemm_x3(ws, g.T, (int)Cin, (int)Cout, wino_points(), s, true);
     Epi o{};
     o.bias = bias; o.scale = bn_scale; o.shift = bn_shift; o.res = residual;
     o.res_mode = residual ? 1 : 0; o.relu = relu; o.z = z_out; o.y = y; o.ldy = Cout;
-    WINO_LAUNCH(wino_output_kernel, dim3(grid_for(g.T * Cout, 256)), dim3(256), 0, s, ws.M,
-                       g, (int)Cout, o);
-    return check_launch("conv3d winograd fwd");
+    WINO_LAUNCH(wino_output_kernel, dim3(grid_for(g.T * Cout, 256)), dim3(256), 0, s, ws.M, g, (int)Cout, o);
+    return check_launch("conv3d winograd fwd (x3)");
 }
 
 extern "C" int m3d_conv3d_fwd_wino(const float* x, int64_t B, int64_t H, int64_t W, int64_t D,
@@ -4855,8 +4752,6 @@ extern "C" int m3d_conv3d_fwd_wino_keep(const float* x, int64_t B, int64_t H, in
                                         float* z_out, float* y, float* u_keep, void* workspace,
                                         size_t ws_bytes, m3d_stream_t s) {
     if (!u_keep) return einval("conv3d winograd: u_keep must not be NULL");
-    if (wino_nz() != wino_wgrad_nz())
-        return einval("conv3d winograd: forward and weight-gradient tiles differ (m3d_conv3d_wino_u_bytes == 0)");
     return fwd_wino(x, B, H, W, D, Cin, w, Cout, OD, pz, bias, bn_scale, bn_shift, residual, relu,
                     z_out, y, u_keep, workspace, ws_bytes, st(s));
 }
@@ -4926,7 +4821,7 @@ static int bwd_data_wino_bn(const float* dz, const float* w, int64_t B, int64_t 
         return einval("conv3d winograd bwd-data (fused BN backward): Cin must divide 256 or be a multiple of it");
     if (wino_per_item(B, H, W, D, OD, Cin, Cout))
         return einval("conv3d winograd bwd-data (fused BN backward): batch past the 32-bit operand bound");
-    const WinoGeom g = wino_geom(B, H, W, D, OD, 2 - pz, wino_dgrad_nz(), ny);
+    const WinoGeom g = wino_geom(B, H, W, D, OD, 2 - pz, ny);
     const int64_t rows = Cin % 256 == 0 ? g.T : (g.T * Cin + 255) / 256;
     Epi e{};
     int rc = bn_fuse_epi(bn, Cin, bn_ws, bn_ws_bytes, rows, e);
@@ -4966,11 +4861,10 @@ extern "C" int m3d_conv3d_bwd_data_wino_bny(const float* dz, const float* w, int
 // offset 0; the forward's form also uses a 27*Cin*Cout fp32 scratch behind them
 // (the transposed weights, x3_wt_kernel).
 static size_t wino_v_planes_bytes(int64_t Cin, int64_t Cout, int dgrad, int ny) {
-    const int P = dgrad ? wino_points(wino_dgrad_nz(), ny) : wino_points();
+    const int P = wino_points(dgrad ? ny : WNY);
     return (6 * (size_t)P * (size_t)Cin * (size_t)Cout + 255) & ~(size_t)255;
 }
 static int wino_v_tile(int32_t dgrad, int32_t tile_y, int& ny) {
-    if (!gemm_x3_env()) return einval("conv3d winograd: external transformed weights need the bf16-split GEMMs");
     if (dgrad) return dgrad_tile_arg(tile_y, ny);
     ny = WNY;
     return M3D_OK;
@@ -4992,16 +4886,13 @@ extern "C" int m3d_conv3d_wino_weight_v(const float* w, int64_t Cin, int64_t Cou
         float* wt = reinterpret_cast<float*>(static_cast<char*>(v) + wino_v_planes_bytes(Cin, Cout, 0, ny));
         hipLaunchKernelGGL(x3_wt_kernel, dim3((unsigned)((Cout + 31) / 32), (unsigned)((Cin + 31) / 32), 27),
                            dim3(256), 0, st(s), w, (int)Cin, (int)Cout, wt);
-        WINO_LAUNCH_NZ_X3(wino_nz(), wino_weight_kernel, grid, dim3(256), 0, st(s), wt, (int)Cin, (int)Cout, 0,
-                          static_cast<float*>(v));
+        hipLaunchKernelGGL((wino_weight_kernel<WNZ, true>), grid, dim3(256), 0, st(s), wt, (int)Cin, (int)Cout, 0,
+                           static_cast<float*>(v));
         return check_launch("conv3d winograd weight transform (fwd)");
     }
-    const int nz = wino_dgrad_nz();
     float* V = static_cast<float*>(v);
-    if (nz == 4 && ny == 4) hipLaunchKernelGGL((wino_weight_kernel<4, true, 4>), grid, dim3(256), 0, st(s), w, (int)Cin, (int)Cout, 1, V);
-    else if (nz == 4) hipLaunchKernelGGL((wino_weight_kernel<4, true, 2>), grid, dim3(256), 0, st(s), w, (int)Cin, (int)Cout, 1, V);
-    else if (ny == 4) hipLaunchKernelGGL((wino_weight_kernel<2, true, 4>), grid, dim3(256), 0, st(s), w, (int)Cin, (int)Cout, 1, V);
-    else hipLaunchKernelGGL((wino_weight_kernel<2, true, 2>), grid, dim3(256), 0, st(s), w, (int)Cin, (int)Cout, 1, V);
+    if (ny == 4) hipLaunchKernelGGL((wino_weight_kernel<WNZ, true, 4>), grid, dim3(256), 0, st(s), w, (int)Cin, (int)Cout, 1, V);
+    else hipLaunchKernelGGL((wino_weight_kernel<WNZ, true, 2>), grid, dim3(256), 0, st(s), w, (int)Cin, (int)Cout, 1, V);
     return check_launch("conv3d winograd weight transform (dgrad)");
 }
 extern "C" int m3d_conv3d_fwd_wino_kv(const float* x, int64_t B, int64_t H, int64_t W, int64_t D, int64_t Cin,
@@ -5009,11 +4900,7 @@ extern "C" int m3d_conv3d_fwd_wino_kv(const float* x, int64_t B, int64_t H, int6
                                       const float* bn_scale, const float* bn_shift, const float* residual,
                                       int32_t relu, float* z_out, float* y, float* u_keep, const void* v,
                                       void* workspace, size_t ws_bytes, m3d_stream_t s) {
-    int ny;
-    if (int rc = wino_v_tile(0, 0, ny)) return rc;
     if (!v) return einval("conv3d winograd: v must not be NULL (m3d_conv3d_wino_weight_v)");
-    if (u_keep && wino_nz() != wino_wgrad_nz())
-        return einval("conv3d winograd: forward and weight-gradient tiles differ (m3d_conv3d_wino_u_bytes == 0)");
     return fwd_wino(x, B, H, W, D, Cin, w, Cout, OD, pz, bias, bn_scale, bn_shift, residual, relu, z_out, y, u_keep,
                     workspace, ws_bytes, st(s), nullptr, 0, 0, false, 0, v);
 }
@@ -5091,7 +4978,7 @@ static int rs_cap(int64_t rows) {
 }
 // whether this call scans dz at all (host side: shapes and the process mode only)
 static bool rs_attempt(int mode, int64_t rows, int64_t Cin, int64_t Cout) {
-    if (mode == RS_OFF || !gemm_x3_env() || !wgrad_x3_env()) return false;
+    if (mode == RS_OFF) return false;
     if (rs_cap(rows) < 1 || rows > 0x7FFFFFFF) return false;
     return mode == RS_ALWAYS || 2.0 * 27.0 * (double)rows * (double)Cin * (double)Cout >= RS_MIN_FLOP;
 }
@@ -5417,7 +5304,7 @@ extern "C" int m3d_conv3d_bwd_data_wino_rs(const float* dz, const float* w, int6
                                            int32_t accumulate, void* workspace, size_t ws_bytes, int32_t v_ready,
                                            int32_t tile_y, const void* v, int32_t rs_mode, m3d_stream_t s) {
     int ny;
-    if (int rc = v ? wino_v_tile(1, tile_y, ny) : dgrad_tile_arg(tile_y, ny)) return rc;
+    if (int rc = dgrad_tile_arg(tile_y, ny)) return rc;
     if (rs_mode < RS_AUTO || rs_mode > RS_ALWAYS) return einval("conv3d winograd bwd-data: rs_mode must be 0, 1 or 2");
     return bwd_data_wino(dz, w, B, H, W, D, Cin, Cout, OD, pz, dx, accumulate, workspace, ws_bytes, st(s), nullptr, 0,
                          v_ready != 0, nullptr, ny, v, rs_mode);
@@ -5426,7 +5313,7 @@ extern "C" int m3d_conv3d_bwd_data_wino_rs(const float* dz, const float* w, int6
 // the data-gradient output transform: dx over the (halo-extended) grid, or,
 // for a depth slab with dx_halo, interior planes into dx (depth dl) and the
 // neighbours' planes into dx_halo [B][H][W][2][C]
-template <int NZ, int NY>
+template <int NY>
 static void wino_dgrad_out(const float* Mt, const WinoGeom& g, int C, float* dx, int accumulate,
                            float* dx_halo, int hlo, int dl, hipStream_t hs, const Epi* fb) {
     Epi o{};
@@ -5434,43 +5321,28 @@ static void wino_dgrad_out(const float* Mt, const WinoGeom& g, int C, float* dx,
     o.y = dx; o.ldy = C; o.accumulate = accumulate;
     const dim3 grid(grid_for(g.T * C, 256));
     if (fb) {
-        hipLaunchKernelGGL((wino_output_bn_kernel<NZ, NY>), grid, dim3(256), 0, hs, Mt, g, C, o);
+        hipLaunchKernelGGL((wino_output_bn_kernel<WNZ, NY>), grid, dim3(256), 0, hs, Mt, g, C, o);
         return;
     }
     if (dx_halo) {
         o.yh = dx_halo; o.hlo = hlo; o.dl = dl;
-        hipLaunchKernelGGL((wino_output_halo_kernel<NZ, NY>), grid, dim3(256), 0, hs, Mt, g, C, o);
+        hipLaunchKernelGGL((wino_output_halo_kernel<WNZ, NY>), grid, dim3(256), 0, hs, Mt, g, C, o);
         return;
     }
-    hipLaunchKernelGGL((wino_output_kernel<NZ, NY>), grid, dim3(256), 0, hs, Mt, g, C, o);
+    hipLaunchKernelGGL((wino_output_kernel<WNZ, NY>), grid, dim3(256), 0, hs, Mt, g, C, o);
 }
 
-// the data gradient's launches on F(NY x 2 x NZ) tiles (geometry g, workspace ws)
-template <int NZ, int NY>
+// the data gradient's launches on F(NY x 2 x 4) tiles (geometry g, workspace ws)
+template <int NY>
 static void bwd_data_wino_launch(const float* dz, const float* w, const WinoGeom& g, const WinoWs& ws, int Cin,
                                  int Cout, float* dx, int32_t accumulate, float* dx_halo, int hlo, int dl,
                                  bool v_ready, const Epi* fb, hipStream_t hs) {
-    const int P = wino_points(NZ, NY);
     const dim3 wgrid(grid_for((int64_t)Cin * Cout, 256)), igrid(grid_for(g.T * Cout, 256));
-    if (gemm_x3_env()) {
-        if (!v_ready)
-            hipLaunchKernelGGL((wino_weight_kernel<NZ, true, NY>), wgrid, dim3(256), 0, hs, w, Cin, Cout, 1, ws.V);
-        const bool af32 = x3_af32_env();
-        if (af32)
-            hipLaunchKernelGGL((wino_input_kernel<NZ, false, false, NY>), igrid, dim3(256), 0, hs, dz, g, Cout, ws.U);
-        else
-            hipLaunchKernelGGL((wino_input_kernel<NZ, true, false, NY>), igrid, dim3(256), 0, hs, dz, g, Cout, ws.U);
-        wino_gemm_x3(ws, g.T, Cout, Cin, P, hs, af32, g.gate);
-    } else {
-        hipLaunchKernelGGL((wino_weight_kernel<NZ, false, NY>), wgrid, dim3(256), 0, hs, w, Cin, Cout, 1, ws.V);
-        hipLaunchKernelGGL((wino_input_kernel<NZ, false, false, NY>), igrid, dim3(256), 0, hs, dz, g, Cout, ws.U);
-        ConvP p = wino_gemm_p(ws.U, g.T, Cout, ws.V, Cin);
-        Epi e{};
-        e.y = ws.M; e.ldy = Cin; e.simple = 1; e.YH = 1; e.YW = 1; e.YD = (int)g.T;
-        e.ysy = e.ysx = e.ysz = 1;
-        dispatch_gemm<false, true>(p, e, hs, P);
-    }
-    wino_dgrad_out<NZ, NY>(ws.M, g, Cin, dx, accumulate, dx_halo, hlo, dl, hs, fb);
+    if (!v_ready)
+        hipLaunchKernelGGL((wino_weight_kernel<WNZ, true, NY>), wgrid, dim3(256), 0, hs, w, Cin, Cout, 1, ws.V);
+    hipLaunchKernelGGL((wino_input_kernel<WNZ, false, false, NY>), igrid, dim3(256), 0, hs, dz, g, Cout, ws.U);
+    wino_gemm_x3(ws, g.T, Cout, Cin, wino_points(NY), hs, true, g.gate);
+    wino_dgrad_out<NY>(ws.M, g, Cin, dx, accumulate, dx_halo, hlo, dl, hs, fb);
 }
 
 static int bwd_data_wino(const float* dz, const float* w, int64_t B, int64_t H, int64_t W, int64_t D,
@@ -5490,13 +5362,13 @@ static int bwd_data_wino(const float* dz, const float* w, int64_t B, int64_t H, 
         }
         return M3D_OK;
     }
-    const int nz = wino_dgrad_nz(), ny = ny_arg ? ny_arg : wino_dgrad_ny();
-    WinoGeom g = wino_geom(B, H, W, D, OD, 2 - pz, nz, ny);
+    const int ny = ny_arg ? ny_arg : wino_dgrad_ny();
+    WinoGeom g = wino_geom(B, H, W, D, OD, 2 - pz, ny);
     // the layout this call uses (its tile_y may differ from the library's default)
-    if (ws_bytes < wino_ws_need(g, Cout, Cin, nz, ny))
+    if (ws_bytes < wino_ws_need(g, Cout, Cin, ny))
         return einval("conv3d winograd: workspace too small");
     // same layout with the roles of Cin/Cout swapped (V'[P][Cout][Cin], U'[P][T][Cout])
-    WinoWs ws = wino_ws(workspace, g, Cout, Cin, nz, ny);
+    WinoWs ws = wino_ws(workspace, g, Cout, Cin, ny);
     float* const ws_u = ws.U;
     if (v_ext) {                        // transformed by m3d_conv3d_wino_weight_v (dgrad 1, this tile_y)
         ws.V = static_cast<float*>(const_cast<void*>(v_ext));
@@ -5507,7 +5379,7 @@ static int bwd_data_wino(const float* dz, const float* w, int64_t B, int64_t H, 
     // outcome and enqueue the sparse launches behind their own gate
     const int64_t rows = B * H * W * OD;
     const int cap = rs_cap(rows);
-    const size_t lay = wino_ws_layout(g, Cout, Cin, nz, ny);
+    const size_t lay = wino_ws_layout(g, Cout, Cin, ny);
     const size_t um = lay - (size_t)(reinterpret_cast<char*>(ws_u) - static_cast<char*>(workspace));
     if (!dx_halo && !fb && rs_attempt(rs_mode, rows, Cin, Cout) && rs_dgrad_bytes(cap, Cin, Cout) <= um &&
         (int64_t)cap * 27 * Cin * 4 < 0xFFFFFFF0LL && 27 * Cin * Cout * 2 < 0xFFFFFFF0LL) {
@@ -5516,14 +5388,10 @@ static int bwd_data_wino(const float* dz, const float* w, int64_t B, int64_t H, 
         rs_dgrad_launch(dz, w, B, (int)H, (int)W, (int)D, (int)OD, pz, ci, co, dx, accumulate,
                         reinterpret_cast<char*>(ws_u), cap, hd, hs);
     }
-    if (nz == 4 && ny == 4)
-        bwd_data_wino_launch<4, 4>(dz, w, g, ws, ci, co, dx, accumulate, dx_halo, hlo, dl, v_ready, fb, hs);
-    else if (nz == 4)
-        bwd_data_wino_launch<4, 2>(dz, w, g, ws, ci, co, dx, accumulate, dx_halo, hlo, dl, v_ready, fb, hs);
-    else if (ny == 4)
-        bwd_data_wino_launch<2, 4>(dz, w, g, ws, ci, co, dx, accumulate, dx_halo, hlo, dl, v_ready, fb, hs);
+    if (ny == 4)
+        bwd_data_wino_launch<4>(dz, w, g, ws, ci, co, dx, accumulate, dx_halo, hlo, dl, v_ready, fb, hs);
     else
-        bwd_data_wino_launch<2, 2>(dz, w, g, ws, ci, co, dx, accumulate, dx_halo, hlo, dl, v_ready, fb, hs);
+        bwd_data_wino_launch<2>(dz, w, g, ws, ci, co, dx, accumulate, dx_halo, hlo, dl, v_ready, fb, hs);
     return check_launch("conv3d winograd bwd-data");
 }
 
@@ -5545,18 +5413,17 @@ static int bwd_weight_wino(const float* x, const float* u_in, const float* dz, i
         }
         return M3D_OK;
     }
-    const int nz = wino_wgrad_nz();
-    WinoGeom g = wino_geom(B, H, W, OD, D, pz, nz);
+    WinoGeom g = wino_geom(B, H, W, OD, D, pz);
     g.halo = halo; g.hlo = hlo; g.hhi = hhi;
-    WinoWs ws = wino_ws(workspace, g, Cin, Cout, nz);   // V <- dW_hat, U <- B^T x, M <- A dz
+    WinoWs ws = wino_ws(workspace, g, Cin, Cout);   // V <- dW_hat, U <- B^T x, M <- A dz
     // row-sparse dz (see rs_scan): the launches below return when the scan finds dz
     // sparse, and dw += xg[tap]^T dzc over the gathered active rows runs in their place
     const int* gate = nullptr;
     const int64_t rows = B * H * W * OD;
     const int cap = rs_cap(rows);
-    const size_t lay = wino_ws_layout(g, Cin, Cout, nz, WNY);
+    const size_t lay = wino_ws_layout(g, Cin, Cout, WNY);
     const size_t um = lay - (size_t)(reinterpret_cast<char*>(ws.U) - static_cast<char*>(workspace));
-    if (x && !halo && wgrad_x3_env() && (Cout > 64 || Cin <= 64) && rs_attempt(rs_mode, rows, Cin, Cout) &&
+    if (x && !halo && (Cout > 64 || Cin <= 64) && rs_attempt(rs_mode, rows, Cin, Cout) &&
         rs_wgrad_bytes(cap, Cin, Cout) <= um) {
         const RsHdr hd = rs_hdr(static_cast<char*>(workspace) + lay, rows);
         gate = g.gate = hd.h + RS_SKIP_DENSE;
@@ -5574,28 +5441,25 @@ static int bwd_weight_wino(const float* x, const float* u_in, const float* dz, i
     if (u_in)
         ws.U = const_cast<float*>(u_in);       // the forward's transformed input, kept
     else
-        WINO_INPUT(nz, false, dim3(grid_for(g.T * Cin, 256)), st(s), x, g, (int)Cin, ws.U);
-    // M3D_WINO_GRAD4=1: the float4 form (measured slower: 278 vs 253 us avg, write-bound)
-        WINO_LAUNCH_NZ(nz, wino_grad_kernel, dim3(grid_for(g.T * Cout, 256)), dim3(256), 0, st(s), dz, g,
-                       (int)Cout, ws.M);
+        WINO_INPUT(dim3(grid_for(g.T * Cin, 256)), st(s), x, g, (int)Cin, ws.U);
+    WINO_LAUNCH(wino_grad_kernel, dim3(grid_for(g.T * Cout, 256)), dim3(256), 0, st(s), dz, g, (int)Cout, ws.M);
     // (Cin, Cout <= 64: x3_wgrad64_kernel, the whole 64x64 product per workgroup)
     int fe = 0;                 // the hipError_t of a failed zero-fill
-    if (wgrad_x3_env() && (Cout > 64 || Cin <= 64)) {
-        fe = launch_wgrad_x3(ws.U, ws.M, ws.V, g.T, (int)Cin, (int)Cout, wino_points(nz), g.T * Cin, g.T * Cout,
+    if (Cout > 64 || Cin <= 64) {
+        fe = launch_wgrad_x3(ws.U, ws.M, ws.V, g.T, (int)Cin, (int)Cout, wino_points(), g.T * Cin, g.T * Cout,
                              (int64_t)Cin * Cout, st(s), true, gate);
-    } else {
+    } else {                                // Cin > 64 -> Cout <= 64: the f32 128x64 tile
         ConvP p = wino_gemm_p(ws.U, g.T, (int)Cin, nullptr, (int)Cout);
         p.bsw = g.T * Cout;                 // dz (DY) batch stride
         p.bsy = (int64_t)Cin * Cout;        // dW_hat batch stride
-        if (Cout <= 64) fe = launch_wgrad<128, 64, 2, 2, true>(p, ws.M, ws.V, st(s), wino_points(nz), true);
-        else fe = launch_wgrad<128, 128, 2, 2, true>(p, ws.M, ws.V, st(s), wino_points(nz), true);
+        fe = launch_wgrad<128, 64, 2, 2, true>(p, ws.M, ws.V, st(s), wino_points(), true);
     }
     if (fe) {
         set_error("memset dW_hat: %s", hipGetErrorString((hipError_t)fe));
         return M3D_EHIP;
     }
-    WINO_LAUNCH_NZ(nz, wino_wgrad_out_kernel, dim3(grid_for(Cin * Cout, 256)), dim3(256), 0, st(s),
-                       ws.V, (int)Cin, (int)Cout, dw, gate);
+    WINO_LAUNCH(wino_wgrad_out_kernel, dim3(grid_for(Cin * Cout, 256)), dim3(256), 0, st(s), ws.V, (int)Cin,
+                (int)Cout, dw, gate);
     return check_launch("conv3d winograd bwd-weight");
 }
 
@@ -5628,8 +5492,6 @@ extern "C" int m3d_conv3d_fwd_wino_halo(const float* x, const float* x_halo, int
                                         m3d_stream_t s) {
     int rc = halo_check(x_halo, has_lo, has_hi);
     if (rc) return rc;
-    if (u_keep && wino_nz() != wino_wgrad_nz())
-        return einval("conv3d winograd: forward and weight-gradient tiles differ (m3d_conv3d_wino_u_bytes == 0)");
     return fwd_wino(x, B, H, W, Dl, Cin, w, Cout, Dl, 1, bias, bn_scale, bn_shift, residual, relu, z_out, y,
                     u_keep, workspace, ws_bytes, st(s), x_halo, has_lo, has_hi);
 }
@@ -5649,8 +5511,6 @@ extern "C" int m3d_conv3d_fwd_wino_halo_phase(const float* x, const float* x_hal
     if (phase != 1 && phase != 2) return einval("conv3d winograd halo: phase must be 1 or 2");
     int rc = phase == 2 ? halo_check(x_halo, has_lo, has_hi) : M3D_OK;
     if (rc) return rc;
-    if (u_keep && wino_nz() != wino_wgrad_nz())
-        return einval("conv3d winograd: forward and weight-gradient tiles differ (m3d_conv3d_wino_u_bytes == 0)");
     return fwd_wino(x, B, H, W, Dl, Cin, w, Cout, Dl, 1, bias, bn_scale, bn_shift, residual, relu, z_out, y,
                     u_keep, workspace, ws_bytes, st(s), phase == 2 ? x_halo : nullptr, has_lo, has_hi, false,
                     phase);
@@ -5696,13 +5556,10 @@ extern "C" size_t m3d_conv3d_rowsparse_header_offset(int64_t B, int64_t H, int64
                                                      int32_t pz, int64_t Cin, int64_t Cout, int32_t pass,
                                                      int32_t tile_y) {
     if (wino_check(B, H, W, D, OD, pz, Cin, Cout) || wino_per_item(B, H, W, D, OD, Cin, Cout)) return (size_t)-1;
-    if (pass == 1) {
-        const int nz = wino_wgrad_nz();
-        return wino_ws_layout(wino_geom(B, H, W, OD, D, pz, nz), Cin, Cout, nz, WNY);
-    }
+    if (pass == 1) return wino_ws_layout(wino_geom(B, H, W, OD, D, pz), Cin, Cout, WNY);
     if (pass != 0 || (tile_y != 0 && tile_y != 2 && tile_y != 4)) return (size_t)-1;
-    const int nz = wino_dgrad_nz(), ny = tile_y ? tile_y : wino_dgrad_ny();
-    return wino_ws_layout(wino_geom(B, H, W, D, OD, 2 - pz, nz, ny), Cout, Cin, nz, ny);
+    const int ny = tile_y ? tile_y : wino_dgrad_ny();
+    return wino_ws_layout(wino_geom(B, H, W, D, OD, 2 - pz, ny), Cout, Cin, ny);
 }
 
 // The kept-U form that also receives x [B,H,W,D,Cin]: the dense launches read u as

@@ -366,13 +366,13 @@ int m3d_conv3d_bwd_weight_wino(const float* x, const float* dz, int64_t B, int64
 /* Training variants: the forward keeps its transformed input U = B^T x B
  * ([64][T][Cin], m3d_conv3d_wino_u_bytes) in caller memory (u_keep) and the
  * weight gradient reuses it instead of transforming x again. */
-/* z extent of the Winograd output tile (4: F(2x2x4), default; 2: F(2x2x2)
- * when M3D_WINO_NZ=2): 16*(NZ+2) batched point GEMMs per conv. */
+/* z extent of the Winograd output tile: 4, F(4,3) along z (4*(NY+2)*6 batched
+ * point GEMMs per conv). */
 int32_t m3d_conv3d_wino_tile_z(void);
-/* z extent of the weight gradient's output tile (4: F(2x2x4), the forward's, whose
- * transformed input the forward keeps -- m3d_conv3d_wino_u_bytes > 0; 2: F(2x2x2)). */
+/* z extent of the weight gradient's output tile: 4, the forward's, whose
+ * transformed input the forward keeps (m3d_conv3d_wino_u_bytes). */
 int32_t m3d_conv3d_wino_wgrad_tile_z(void);
-int32_t m3d_conv3d_wino_tile_y(void);   /* output tile rows along y (2: F(2,3), 4: F(4,3)) */
+int32_t m3d_conv3d_wino_tile_y(void);   /* output tile rows along y: 4, F(4,3) */
 /* the data gradient's tile (m3d_conv3d_bwd_data_wino*): F(2,3) along y by
  * default (F(2x2x4)) beside the forward's F(4x2x4) -- the accuracy of the
  * gradients every earlier layer receives */
@@ -516,7 +516,7 @@ int m3d_conv3d_bwd_data_wino_bny(const float* dz, const float* w, int64_t B, int
  * stream at the start of the forward) and pass them to the _kv / _xv entries,
  * which then skip their own transform (same kernels, same bits).  dgrad 0: the
  * forward's operand; 1: the data gradient's at tile_y (0 = library default, 2,
- * 4).  Requires the bf16-split GEMMs (0 bytes / M3D_EINVAL otherwise). */
+ * 4). */
 size_t m3d_conv3d_wino_v_bytes(int64_t Cin, int64_t Cout, int32_t dgrad, int32_t tile_y);
 int m3d_conv3d_wino_weight_v(const float* w, int64_t Cin, int64_t Cout, int32_t dgrad, int32_t tile_y, void* v,
                              size_t v_bytes, m3d_stream_t s);
@@ -551,8 +551,8 @@ int m3d_conv3d_bwd_data_splitk_bn(const float* dz, const float* w, int64_t B, in
 /* Plain batched fp32 GEMM on the same MFMA kernel: for b < batch,
  * C[b] = act(A[b] B[b] + bias) (+ C[b] if accumulate); A [M][K], B [K][N],
  * C [M][N] row-major, batches contiguous; N multiple of 4.  The Winograd
- * point-wise products above run this f32-MFMA kernel with M3D_GEMM_X3=0 (by
- * default they run x3_gemm_kernel on the exact bf16 split, conv3d.hip). */
+ * point-wise products above do not run it: they run the x3_gemm kernels on
+ * the exact bf16 split (conv3d.hip). */
 int m3d_gemm_f32(const float* A, const float* B, float* C, int64_t batch, int64_t M, int64_t K,
                  int64_t N, const float* bias, int32_t relu, int32_t accumulate, m3d_stream_t s);
 
@@ -579,7 +579,7 @@ int m3d_gemm_x3(const uint16_t* A3, const uint16_t* B3, float* C, int64_t batch,
                 int64_t N, m3d_stream_t s);
 /* m3d_gemm_x3 with A as fp32 [batch][M][K], split in the GEMM on its way into
  * LDS (x3_gemm256_af_kernel for N % 256 == 0, else x3_gemm_kernel<AF32>): the
- * form the Winograd point GEMMs run in the step (M3D_GEMM_X3 bit 4, default),
+ * form the Winograd point GEMMs run in the step,
  * bit-identical to m3d_gemm_x3 on the split planes of the same A. */
 int m3d_gemm_x3_af(const float* A, const uint16_t* B3, float* C, int64_t batch, int64_t M, int64_t K,
                    int64_t N, m3d_stream_t s);

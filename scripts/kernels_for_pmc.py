@@ -23,7 +23,7 @@ if leg == "gemm":
 elif leg == "wgrad":
     print(bench.time_wgrad_gemm(S, reps=20))
 elif leg == "winofwd":
-    # rpn_conv_shared1 on P2 as a Winograd conv through the C-ABI (M3D_GEMM_X3 picks the GEMM)
+    # rpn_conv_shared1 on P2 as a Winograd conv through the C-ABI
     from m3d import _lib
     L = _lib.load()
     B, H, W, D, Cin, Cout = 1, S // 4, S // 4, S, 256, 512

@@ -46,8 +46,8 @@ U = 2.0 ** -24
 
 # compile-time tuning defaults of csrc/common.h that the dispatch reads
 # (tests/test_convref.py compares them with the header)
-TUNE = {"M3D_TUNE_GEMM_X3": 31, "M3D_TUNE_WGRAD_MINM": 512, "M3D_TUNE_X3W_TR": 1, "M3D_TUNE_X3W_TR_MINM": 256,
-        "M3D_TUNE_X3W_SK": 1, "M3D_TUNE_X3W_SK_MIN_STEPS": 32, "M3D_TUNE_WGRAD1_X3_MIN_N": 65}
+TUNE = {"M3D_TUNE_WGRAD_MINM": 512, "M3D_TUNE_X3W_TR_MINM": 256, "M3D_TUNE_X3W_SK_MIN_STEPS": 32,
+        "M3D_TUNE_WGRAD1_X3_MIN_N": 65}
 W2_BK = 16                      # conv3d.hip: rows per step of x3_wgrad_tr_kernel
 NCU = 256                       # MI355X
 # smallest CU count at which the persistent cases can be sized at all:
@@ -252,13 +252,12 @@ RELU_CAP = 1e-3                 # of a tensor's elements
 # --------------------------------------------------------------------------- dispatch
 def gemm_path(M, N, K, nbatch, bt, avec, epi_flags, ncu=NCU):
     """The conv_gemm_kernel instantiation dispatch_gemm<BT, AVEC> /
-    launch_gemm (conv3d.hip:1196-1257) launch for a GEMM of M rows, N columns,
+    launch_gemm launch for a GEMM of M rows, N columns,
     nbatch batches: ("gemm", BM, BN, "bt" | "nt", "avec" | "scalar", "x3" | "f32",
     "persist" | "grid", "fbn" | "").  epi_flags: the names of whatever makes the
-    epilogue not "plain" (launch_gemm:1218: bias, scale, res, act, z, split,
+    epilogue not "plain" (launch_gemm: bias, scale, res, act, z, split,
     accumulate, deconv, fbn, ldy % 4); "fbn" selects the fused-BN form.  K does
     not steer the dispatch (BK = 32 everywhere; a BK = 64 form is never launched)."""
-    x3_conv = (TUNE["M3D_TUNE_GEMM_X3"] >> 1) & 1
     if N <= 32:
         bm, bn = 128, 32
     elif N <= 64:
@@ -268,17 +267,17 @@ def gemm_path(M, N, K, nbatch, bt, avec, epi_flags, ncu=NCU):
         bm, bn = (64, 128) if blocks128 < 512 else (128, 128)
     t = "bt" if bt else "nt"
     if bt and "fbn" in epi_flags:
-        return ("gemm", bm, bn, t, "avec" if avec else "scalar", "x3" if avec and x3_conv else "f32", "grid", "fbn")
+        return ("gemm", bm, bn, t, "avec" if avec else "scalar", "x3" if avec else "f32", "grid", "fbn")
     if not avec:
         return ("gemm", bm, bn, t, "scalar", "f32", "grid", "")       # NBUF = 2
     tiles = cdiv(M, bm) * cdiv(N, bn) * nbatch
     persist = nbatch > 1 and not epi_flags and tiles > 2 * (ncu * 3)
-    x3 = (bt or bn >= 64) and x3_conv
+    x3 = bt or bn >= 64
     return ("gemm", bm, bn, t, "avec", "x3" if x3 else "f32", "persist" if persist else "grid", "")
 
 
 def _wg_out(splits, per, det, scratch_floats):
-    """wg_out (conv3d.hip:940-955): (splits, target)"""
+    """wg_out: (splits, target)"""
     if not det:
         return splits, "atomic"
     fit = scratch_floats // per
@@ -288,8 +287,8 @@ def _wg_out(splits, per, det, scratch_floats):
 
 
 def _m_splits(M, tiles, minm, mround, det, scratch_floats, per, aim=1024):
-    """the split arithmetic shared by launch_wgrad (conv3d.hip:1266-1283) and
-    launch_wgrad_x3 (1828-1864): (splits, mper, target)"""
+    """the split arithmetic shared by launch_wgrad and
+    launch_wgrad_x3: (splits, mper, target)"""
     splits = max(1, min(cdiv(aim, tiles), cdiv(M, minm)))
     splits, target = _wg_out(splits, per, det, scratch_floats)
     mper = cdiv(cdiv(M, splits), mround) * mround
@@ -297,9 +296,9 @@ def _m_splits(M, tiles, minm, mround, det, scratch_floats, per, aim=1024):
 
 
 def wgrad_path(M, Cin, taps, Cout, unit_s1, det=False, scratch_floats=0, ncu=NCU):
-    """The kernel m3d_conv3d_bwd_weight (conv3d.hip:4118-4160) launches, with
-    launch_wgrad (1266-1283), launch_wgrad_x3 (1828-1864), launch_wgrad_tr
-    (1781-1822) and wg_out (940-955): (instantiation, target, splits, mper).  The
+    """The kernel m3d_conv3d_bwd_weight launches, with
+    launch_wgrad, launch_wgrad_x3, launch_wgrad_tr
+    and wg_out: (instantiation, target, splits, mper).  The
     instantiation names the kernel and its template arguments; target is where
     its partial tiles go ("atomic", "reduce" = wg_reduce_kernel, "plain").  splits
     is the number of additions one dW element receives (an upper bound on the
@@ -307,11 +306,11 @@ def wgrad_path(M, Cin, taps, Cout, unit_s1, det=False, scratch_floats=0, ncu=NCU
     K, N = taps * Cin, Cout
     vec = Cin % 4 == 0
     minm = TUNE["M3D_TUNE_WGRAD_MINM"]
-    if vec and (TUNE["M3D_TUNE_GEMM_X3"] >> 3) & 1 and unit_s1 and Cout >= TUNE["M3D_TUNE_WGRAD1_X3_MIN_N"]:
-        if TUNE["M3D_TUNE_X3W_TR"] and K >= 192 and N >= 192:
+    if vec and unit_s1 and Cout >= TUNE["M3D_TUNE_WGRAD1_X3_MIN_N"]:
+        if K >= 192 and N >= 192:
             tiles = cdiv(K, 256) * cdiv(N, 256)
             trm = TUNE["M3D_TUNE_X3W_TR_MINM"]
-            if TUNE["M3D_TUNE_X3W_SK"] and not det and M >= TUNE["M3D_TUNE_X3W_SK_MIN_STEPS"] * W2_BK:
+            if not det and M >= TUNE["M3D_TUNE_X3W_SK_MIN_STEPS"] * W2_BK:
                 nk, tn = cdiv(M, W2_BK), cdiv(N, 256)
                 units = tiles * nk
                 G = max(min(cdiv(units, cdiv(trm, W2_BK)), ncu) // tn * tn, tn)

@@ -6,16 +6,18 @@ instantiations written out below.  No GPU.
 
 Both sides are float64 here, so agreement is to 1e-12 of the result's scale.
 
-Instantiations of conv_gemm_kernel<BM, BN, .., BT, AVEC, BK, NBUF, PERSIST, X3,
-FBN> that the default build (M3D_TUNE_GEMM_X3 = 31) never launches, and so no
-test runs:
+Forms of conv_gemm_kernel<BM, BN, .., BT, AVEC, BK, NBUF, PERSIST, X3, FBN>
+that no launch site names, so the library does not hold them
+(test_library_holds_only_launchable_conv_kernels reads its kernel list):
 * every BK = 64 form: dispatch_gemm passes BK = 32 only;
 * X3 = false with AVEC and (BT or BN >= 64), with or without FBN: launch_gemm
-  takes the bf16-split form whenever bit 1 of M3D_TUNE_GEMM_X3 is set;
+  takes the bf16-split form wherever there is one;
 * NBUF = 2 with AVEC: the vector loader always runs one LDS stage;
-* scalar A with BT: every BT caller (data gradient, deconv, split-K) is vector;
-* PERSIST at 64x128: that tile is chosen below 512 blocks of 128 rows, which
-  are at most 1022 tiles of 64 rows, fewer than 6 * 256 CUs.
+* scalar A with BT: every BT caller (data gradient, deconv, split-K) is vector.
+In the library but never launched, and so run by no test:
+* PERSIST at 64x128 (launch_gemm instantiates it with the other tiles): that
+  tile is chosen below 512 blocks of 128 rows, which are at most 1022 tiles of
+  64 rows, fewer than 6 * 256 CUs.
 Reachable but left to other files: the fused-BN forms
 (tests/test_gpu_bnfuse.py), the HALO forms of conv_wgrad_kernel
 (tests/test_gpu_slab_halo.py) and the stem kernels (tests/test_gpu_conv.py,
@@ -237,9 +239,100 @@ def test_tuning_constants_match_the_header():
     for name, v in R.TUNE.items():
         m = re.search(r"#ifndef %s\n#define %s (\d+)" % (name, name), src)
         assert m and int(m.group(1)) == v, name
-    hip = open(os.path.join(ROOT, "3d-mask-r-cnn_amd", "csrc", "conv3d.hip")).read()
+    # the dispatch reads no other constant: the retired form switches are not defined any more
+    for name in ("GEMM_X3", "X3W_TR", "X3W_SK", "WINO_NZ", "WINO_WGRAD_NZ", "WINO_NY"):
+        assert not re.search(r"M3D_TUNE_%s\b" % name, src), name
+    hip =open(os.path.join(ROOT, "3d-mask-r-cnn_amd", "csrc", "conv3d.hip")).read()
     assert "constexpr int W2_BK = %d;" % R.W2_BK in hip
     assert R.TUNE["M3D_TUNE_WGRAD1_X3_MIN_N"] == 65 and R.DET_SMALL_BYTES == 4096
+
+
+# conv_gemm_kernel / conv_wgrad_kernel forms that other files run
+FBN_FORMS = [("gemm", bm, bn, "bt", "avec", "x3", "grid", "fbn") for bm, bn in TILES]   # tests/test_gpu_bnfuse.py
+HALO_FORMS = [("wgrad", 128, 64, "vec", "halo"), ("wgrad", 128, 64, "scalar", "halo"),  # tests/test_gpu_slab_halo.py
+              ("wgrad", 128, 128, "vec", "halo"), ("wgrad", 128, 128, "scalar", "halo")]
+# launch_gemm instantiates the persistent loop for every vector tile; dispatch_gemm never picks it at
+# 64x128 (module docstring)
+NEVER_CHOSEN_PERSIST_64X128 = [_gemm(64, 128, "nt", "avec", "x3", "persist"),
+                               _gemm(64, 128, "bt", "avec", "x3", "persist")]
+# the Winograd transforms and the bf16-split GEMMs, each with what launches it
+WINO_X3_KERNELS = {
+    # F(4,3) along z everywhere; the last argument of the transforms is the y tile
+    "wino_input_kernel<4, false, false, 4>": "m3d_conv3d_fwd_wino*, m3d_conv3d_bwd_weight_wino, bwd_data_wino* tile_y 4",
+    "wino_input_kernel<4, false, false, 2>": "m3d_conv3d_bwd_data_wino* (tile_y 2, the default)",
+    "wino_input_kernel<4, false, true, 4>": "m3d_conv3d_fwd_wino_halo / _halo_phase, m3d_conv3d_bwd_weight_wino_halo",
+    "wino_weight_kernel<4, true, 4>": "m3d_conv3d_fwd_wino*, m3d_conv3d_wino_weight_v, bwd_data_wino* tile_y 4",
+    "wino_weight_kernel<4, true, 2>": "m3d_conv3d_bwd_data_wino*, m3d_conv3d_wino_weight_v (dgrad, tile_y 2)",
+    "wino_output_kernel<4, 4>": "m3d_conv3d_fwd_wino*, bwd_data_wino_vy / _xv / _rs tile_y 4",
+    "wino_output_kernel<4, 2>": "m3d_conv3d_bwd_data_wino* (tile_y 2)",
+    "wino_output_bn_kernel<4, 4>": "m3d_conv3d_bwd_data_wino_bny / _xv tile_y 4",
+    "wino_output_bn_kernel<4, 2>": "m3d_conv3d_bwd_data_wino_bn, _bny / _xv tile_y 2",
+    "wino_output_halo_kernel<4, 2>": "m3d_conv3d_bwd_data_wino_halo",
+    # the halo entry takes no tile_y: this one runs only in a build with M3D_TUNE_WINO_DGRAD_NY 0 or 4
+    # (bwd_data_wino_launch<4> names the halo output beside the other two)
+    "wino_output_halo_kernel<4, 4>": "m3d_conv3d_bwd_data_wino_halo where the library's data-gradient y tile is 4",
+    "wino_grad_kernel<4>": "m3d_conv3d_bwd_weight_wino*",
+    "wino_wgrad_out_kernel<4>": "m3d_conv3d_bwd_weight_wino*",
+    "x3_gemm256_af_kernel<0>": "Winograd fwd / bwd-data point GEMMs (N % 256 == 0), m3d_gemm_x3_af, m3d_conv3d_fwd_x3",
+    "x3_gemm256_af_kernel<1>": "m3d_conv3d_fwd_x3 with an epilogue",
+    "x3_gemm256_af_kernel<2>": "m3d_conv3d_bwd_data_x3_bn / _bna",
+    "x3_gemm256_kernel<0>": "m3d_gemm_x3 (N % 256 == 0)",
+    "x3_gemm_kernel<32, false, 2, true, 128>": "Winograd fwd / bwd-data point GEMMs (other N), m3d_gemm_x3_af",
+    "x3_gemm_kernel<32, false, 2, true, 64>": "Winograd fwd / bwd-data point GEMMs (N = 64), m3d_gemm_x3_af",
+    "x3_gemm_kernel<32, false, 3, false, 128>": "m3d_gemm_x3",
+    "x3_gemm_kernel<32, false, 3, false, 64>": "m3d_gemm_x3 (N = 64)",
+    "x3_wgrad_tr_kernel<0, true>": "m3d_conv3d_bwd_weight_wino*, m3d_conv3d_bwd_weight (1x1x1), m3d_gemm_wgrad_f32: stream-K",
+    "x3_wgrad_tr_kernel<0, false>": "the same, deterministic or below 32 steps: the split grid",
+    "x3_wgrad_kernel<2>": "the same entries, K or N < 192",
+    "x3_wgrad64_kernel<2>": "the same entries, K or N <= 64",
+}
+
+
+def _conv_kernels_of_the_library():
+    """{kernel<template arguments>} of the conv kernels' host handles in libm3d.so (names only)"""
+    import subprocess
+    import m3d._lib as lib
+    out = subprocess.run(["readelf", "-sW", "--demangle", lib.LIB_PATH], capture_output=True, text=True,
+                         check=True).stdout
+    names = set()
+    for line in out.splitlines():
+        f = line.split()
+        if len(f) < 8 or f[3] != "OBJECT" or f[6] == "UND":
+            continue
+        m = re.match(r"(?:void )?(?:m3d::)?((?:conv_gemm|conv_wgrad|wino_\w+|x3_gemm\w*|x3_wgrad\w*)_kernel<[^>]*>)\(",
+                     " ".join(f[7:]))
+        if m:
+            names.add(m.group(1))
+    return names
+
+
+def _form(name):
+    """a conv_gemm_kernel / conv_wgrad_kernel instantiation in the tuple form of REACHABLE"""
+    kern, args = name[:-1].split("<")
+    a = [{"true": True, "false": False}.get(v, v) for v in args.split(", ")]
+    a = [v if isinstance(v, bool) else int(v) for v in a]
+    if kern == "conv_wgrad_kernel":
+        bi, bj, wi, wj, avec, halo = a
+        assert (wi, wj) == (2, 2), name
+        return ("wgrad", bi, bj, "vec" if avec else "scalar") + (("halo",) if halo else ())
+    bm, bn, wm, wn, bt, avec, bk, nbuf, persist, x3, fbn = a
+    assert (wm, wn) == ((4, 1) if bm == 128 and bn <= 64 else (2, 2)) and bk == 32 and nbuf == (1 if avec else 2), name
+    return ("gemm", bm, bn, "bt" if bt else "nt", "avec" if avec else "scalar", "x3" if x3 else "f32",
+            "persist" if persist else "grid", "fbn" if fbn else "")
+
+
+def test_library_holds_only_launchable_conv_kernels():
+    """The built library's conv kernels are the reachable instantiations and nothing else: a form that
+    no entry point can launch (the losing side of a settled A/B) is not compiled in."""
+    names = _conv_kernels_of_the_library()
+    gemm = sorted(n for n in names if n.startswith(("conv_gemm_kernel<", "conv_wgrad_kernel<")))
+    forms = [_form(n) for n in gemm]
+    assert len(set(forms)) == len(forms) > 0
+    want = [p for p in REACHABLE if p[0] in ("gemm", "wgrad")] + FBN_FORMS + HALO_FORMS + NEVER_CHOSEN_PERSIST_64X128
+    assert len(set(want)) == len(want)
+    assert set(forms) == set(want), (sorted(set(forms) - set(want)), sorted(set(want) - set(forms)))
+    rest = names - set(gemm)
+    assert rest == set(WINO_X3_KERNELS), (sorted(rest - set(WINO_X3_KERNELS)), sorted(set(WINO_X3_KERNELS) - rest))
 
 
 @pytest.mark.parametrize("ncu", [R.NCU, R.MIN_NCU])

@@ -638,7 +638,7 @@ def test_wino_shared_weight_transform_bit_identical(cuda):
 def test_wino_weight_gradient_accuracy(cuda, cin, cout):
     """The Winograd weight gradient (the step's 3^3 convs with >= 64 channels;
     64 -> 64 runs x3_wgrad64_kernel, 64 -> 128 x3_wgrad_kernel,
-    F(2x2x4) tiles by default, M3D_WINO_WGRAD_NZ=2 for F(2x2x2)) against
+    on the forward's F(4x2x4) tiles) against
     float64: the fp32 summation over the tiles passes through G^T, whose F(4,3)
     rows amplify it -- held to 2e-5 of the gradient's scale (the direct fp32
     weight gradient's own error is ~1e-6 here), with the measured value printed."""

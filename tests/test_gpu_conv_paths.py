@@ -67,9 +67,9 @@ or above the threshold and 64 the multiple of 4 below it.
 wg_reduce_kernel: the det / det-fit2 modes of every case with M > 512; the "plain" single writer: every
 det-small mode and the det modes of the single-split cases.
 
-Not run here (tests/test_convref.py lists them with the reasons): instantiations the default build
-never launches (BK = 64, the non-split forms of the vector loader at BT or BN >= 64, persistent 64x128);
-the fused-BN forms (tests/test_gpu_bnfuse.py); the HALO forms (tests/test_gpu_slab_halo.py); the stem
+Not run here (tests/test_convref.py lists them with the reasons): the persistent 64x128 forms, which the
+library holds and dispatch_gemm never picks (forms that no launch site names -- BK = 64, the non-split
+forms of the vector loader at BT or BN >= 64 -- are not in the library); the fused-BN forms (tests/test_gpu_bnfuse.py); the HALO forms (tests/test_gpu_slab_halo.py); the stem
 kernels.
 """
 import ctypes
