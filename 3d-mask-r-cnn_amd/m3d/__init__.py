@@ -9,6 +9,9 @@ Drop-in surface:
   m3d.heads    classifier / mask heads, DetectionLayer, MaskRCNN (detect, head_losses)
   m3d.head_losses  mrcnn_losses (+ mrcnn_class_loss / mrcnn_bbox_loss / mrcnn_mask_loss,
                active_class_ids_from_meta): core/models.py:1676-1960, value + gradient
+  m3d.headstore  the stored head targets of TARGET_GENERATION (core/models.py:3530-3796): float16 /
+               bit-packed forms made and read back on the GPU; ToyHeadDataset (m3d.dataset),
+               HeadGenerator (m3d.generator), MaskRCNN.head_target_generation / train_heads_on_features
   m3d.config   Config / load_config (core/config.py)
   m3d.parallel depth-slab sharding + RCCL gradient all-reduce
 All compute runs in libm3d.so (hand-written HIP for gfx950); there is no CPU

@@ -205,6 +205,13 @@ _SIGS = {
                           c_p, c_p, c_sz, c_p],
     "m3d_flip_masks_u8": [c_p, c_i64, c_i64, c_i64, c_i64, c_i32, c_p, c_p],
     "m3d_flip_boxes": [c_p, c_i64, c_i64, c_i64, c_i64, c_i32, c_p, c_p],
+    "m3d_pack_bits_f32": [c_p, c_i64, c_p, c_p],
+    "m3d_f32_to_f16": [c_p, c_i64, c_p, c_p],
+    "m3d_bits_row_counts": [c_p, c_i64, c_i64, c_p, c_p],
+    "m3d_unpack_gather_bits": [c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_p, c_i64, c_i64,
+                               c_i64, c_p, c_p],
+    "m3d_unpack_gather_f16": [c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_p, c_i64, c_i64,
+                              c_i64, c_p, c_p],
     "m3d_maxpool3d_fwd": [c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32,
                           c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, c_p, c_p, c_p],
     "m3d_maxpool3d_bwd": [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32,

@@ -201,3 +201,172 @@ class ToyDataset(Dataset):
             img = imread(info["path"])
             masks = np.zeros((img.shape[1], img.shape[2], img.shape[0], 0), np.float32)
         return boxes, class_ids, masks
+
+
+class ToyHeadDataset(Dataset):
+    """The head dataset TARGET_GENERATION leaves (core/data_generators.py:
+    1720-2023; written by m3d.headstore / MaskRCNN.head_target_generation):
+    ``<data_dir>/datasets/{train,test}.csv`` with the columns rois,
+    rois_aligned, mask_aligned, target_class_ids, target_bbox, target_mask
+    (matched case-insensitively, by the reference's alternative names and by
+    substring; the first, second and fourth are required), each cell the path
+    of one image's ``.npz`` (or plain ``.npy``) file."""
+
+    def __init__(self, config=None):
+        super().__init__()
+        self.config = config
+        self.num_classes = int(getattr(config, "NUM_CLASSES", 2)) if config is not None else 2
+
+    def load_dataset(self, data_dir, is_train=True):
+        import csv
+        self.add_class("dataset", 1, "neuron")
+        split = "train" if is_train else "test"
+        with open(os.path.join(data_dir, "datasets", f"{split}.csv"), newline="") as f:
+            sample = f.read(4096)
+            f.seek(0)
+            try:
+                dialect = csv.Sniffer().sniff(sample, delimiters=",;\t")
+            except csv.Error:
+                dialect = csv.excel
+            rows = [r for r in csv.reader(f, dialect) if r]
+        if not rows:
+            raise ValueError(f"[ToyHeadDataset.load_dataset] {split}.csv is empty")
+        header, rows = rows[0], rows[1:]
+        cols = {c.strip().lower(): i for i, c in enumerate(header)}
+
+        def pick(*cands, required=True):
+            for c in cands:
+                k = c.lower()
+                if k in cols:
+                    return cols[k]
+                for lc, i in cols.items():
+                    if k in lc:
+                        return i
+            if required:
+                raise KeyError(f"[ToyHeadDataset.load_dataset] none of columns {cands} found. Available: {header}")
+            return None
+
+        col = {"rois": pick("rois", "rois_path", "r_path"),
+               "ra_path": pick("rois_aligned", "ra_path", "aligned_rois", "roisAligned"),
+               "ma_path": pick("mask_aligned", "ma_path", "aligned_mask", required=False),
+               "tci_path": pick("target_class_ids", "tci_path", "tci"),
+               "tb_path": pick("target_bbox", "tb_path", "bbox", required=False),
+               "tm_path": pick("target_mask", "tm_path", "tm", required=False)}
+        for i, row in enumerate(rows):
+            info = {k: (row[c] if c is not None and c < len(row) and row[c] else None) for k, c in col.items()}
+            for k, nm in (("rois", "rois"), ("ra_path", "rois_aligned"), ("tci_path", "target_class_ids")):
+                if not info[k]:
+                    raise ValueError(f"[ToyHeadDataset] bad '{nm}' at row {i}")
+            self.add_image("dataset", image_id=i, path=os.path.basename(info["rois"]), **info)
+
+    def prepare(self, class_map=None):
+        super().prepare(class_map)
+        self.num_classes = max(self.num_classes, len(self.class_info))
+
+    @staticmethod
+    def _load_any(path):
+        """An .npz as a dict of its arrays, a plain .npy under "arr_0", None for no file."""
+        if path is None:
+            return None
+        if str(path).endswith(".npz"):
+            with np.load(path, allow_pickle=False) as z:
+                return {k: z[k] for k in z.files}
+        return {"arr_0": np.load(path, allow_pickle=False)}
+
+    @staticmethod
+    def _pick(z, *keys):
+        if z is None:
+            return None
+        for k in keys:
+            if k in z:
+                return z[k]
+        return next(iter(z.values()))
+
+    def filter_by_positive_count(self, min_positive=20):
+        """Keep the images with at least ``min_positive`` positive target class
+        ids (call after prepare()); returns the (name, count) pairs dropped."""
+        keep, skipped = [], []
+        for image_id in self.image_ids:
+            info = self.image_info[int(image_id)]
+            tci = self._pick(self._load_any(info["tci_path"]), "tci", "target_class_ids", "arr_0")
+            n = int(np.sum(tci > 0))
+            if n >= int(min_positive):
+                keep.append(int(image_id))
+            else:
+                skipped.append((info["path"], n))
+        self._image_ids = np.array(keep, dtype=np.int64)
+        return skipped
+
+    def _small(self, info):
+        rois = self._pick(self._load_any(info["rois"]), "rois", "roi", "arr_0")
+        tci = self._pick(self._load_any(info["tci_path"]), "tci", "target_class_ids", "arr_0")
+        tb = self._pick(self._load_any(info["tb_path"]), "bbox", "target_bbox", "arr_0")
+        rois = np.asarray(rois, np.float32)
+        tci = np.asarray(tci, np.int32)
+        tb = np.zeros((rois.shape[0], 6), np.float32) if tb is None else np.asarray(tb, np.float32)
+        return rois, tci, tb
+
+    def load_data(self, image_id):
+        """-> rois [T,6] f32, rois_aligned [T,P,P,P,C] f32, mask_aligned
+        [T,M,M,M,C] f32, target_class_ids [T] i32, target_bbox [T,6] f32,
+        target_mask [T,m,m,m,1] f32, on the host (core/data_generators.py:
+        1873-2023).  A missing mask_aligned / target_bbox / target_mask column is
+        zeros of the configuration's shape."""
+        info = self.image_info[image_id]
+        rois, tci, tb = self._small(info)
+        T = rois.shape[0]
+        ra = np.asarray(self._pick(self._load_any(info["ra_path"]), "rois_aligned", "ra", "arr_0"), np.float32)
+
+        def unbit(z, bits_key, shape_key, fallback):
+            if z is None:
+                return None
+            if bits_key in z and shape_key in z:
+                shape = tuple(int(v) for v in z[shape_key])
+                flat = np.unpackbits(z[bits_key])
+                need = int(np.prod(shape))
+                if flat.shape[0] < need:
+                    flat = np.pad(flat, (0, need - flat.shape[0]))
+                x = flat[:need].reshape(shape)
+            else:
+                x = np.asarray(self._pick(z, fallback))
+            if x.ndim == 4:
+                x = x[..., np.newaxis]
+            return x.astype(np.float32) if x.ndim == 5 else None
+
+        ma = unbit(self._load_any(info["ma_path"]), "mask_bits", "mask_shape", "mask_aligned")
+        tm = unbit(self._load_any(info["tm_path"]), "tm_bits", "tm_shape", "tm")
+        cfg = self.config
+        if ma is None:
+            M, C = int(getattr(cfg, "MASK_POOL_SIZE", 14)), int(getattr(cfg, "TOP_DOWN_PYRAMID_SIZE", 256))
+            ma = np.zeros((T, M, M, M, C), np.float32)
+        if tm is None:
+            m = int(cfg.MASK_SHAPE[0]) if cfg is not None and hasattr(cfg, "MASK_SHAPE") else 28
+            tm = np.zeros((T, m, m, m, 1), np.float32)
+        return rois, ra, ma, tci, tb, tm
+
+    def load_packed(self, image_id, device):
+        """The stored forms as they are, for m3d.headstore.unpack_gather: a dict
+        with ``rois_aligned`` (float16 device tensor [T,P,P,P,C]), ``mask_bits``
+        / ``tm_bits`` (packed uint8 device tensors) with their logical
+        ``mask_shape`` / ``tm_shape`` (tuples), and ``rois`` / ``target_class_ids``
+        / ``target_bbox`` on the host.  Only the .npz layout of
+        m3d.headstore is read this way; use load_data for anything else."""
+        import torch
+        info = self.image_info[image_id]
+        rois, tci, tb = self._small(info)
+        ra = self._load_any(info["ra_path"])
+        ma = self._load_any(info["ma_path"])
+        tm = self._load_any(info["tm_path"])
+        if (ra is None or "rois_aligned" not in ra or ra["rois_aligned"].dtype != np.float16 or ma is None
+                or not {"mask_bits", "mask_shape"} <= set(ma) or tm is None
+                or not {"tm_bits", "tm_shape"} <= set(tm)):
+            raise ValueError(f"[ToyHeadDataset.load_packed] image {image_id} is not stored as float16 rois_aligned "
+                             "and bit-packed mask_aligned / target_mask")
+
+        def up(a):
+            return torch.from_numpy(np.ascontiguousarray(a)).to(device)
+
+        return {"rois": rois, "target_class_ids": tci, "target_bbox": tb,
+                "rois_aligned": up(ra["rois_aligned"]),
+                "mask_bits": up(ma["mask_bits"]), "mask_shape": tuple(int(v) for v in ma["mask_shape"]),
+                "tm_bits": up(tm["tm_bits"]), "tm_shape": tuple(int(v) for v in tm["tm_shape"])}

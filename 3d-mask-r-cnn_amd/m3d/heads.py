@@ -817,13 +817,7 @@ class MaskRCNN:
         With heads=("classifier",) it is train_classifier_head.  The join of the
         two pooled gradients through PyramidROIAlign's backward into the trunk is
         not built."""
-        from . import nn as mnn
-        from .head_losses import active_class_ids_from_meta, mrcnn_losses
-        from .optim import apply_max_norm
-        from .params import CHUNK
-        heads = tuple(heads)
-        if not heads or len(set(heads)) != len(heads) or any(h not in ("classifier", "mask") for h in heads):
-            raise ValueError('train_heads: heads must be a non-empty subset of ("classifier", "mask")')
+        heads = MaskRCNN._check_heads(heads, "train_heads")
         cls, msk = "classifier" in heads, "mask" in heads
         ops._dev(image, image_meta, gt_class_ids, gt_boxes, gt_masks)
         pooled = mpooled = None
@@ -834,6 +828,38 @@ class MaskRCNN:
                 pooled = self.roi_align_classifier([rois, image_meta] + mrcnn_maps)
             if msk:
                 mpooled = self.roi_align_mask([rois, image_meta] + mrcnn_maps)
+        r = self.train_heads_on_features(pooled, mpooled, image_meta, target_class_ids, target_bbox, target_mask,
+                                         optimizer, heads=heads)
+        r["rois"] = rois
+        return r
+
+    @staticmethod
+    def _check_heads(heads, what):
+        heads = tuple(heads)
+        if not heads or len(set(heads)) != len(heads) or any(h not in ("classifier", "mask") for h in heads):
+            raise ValueError(f'{what}: heads must be a non-empty subset of ("classifier", "mask")')
+        return heads
+
+    def train_heads_on_features(self, rois_aligned, mask_aligned, image_meta, target_class_ids, target_bbox,
+                                target_mask, optimizer, heads=("classifier", "mask")):
+        """Steps 2-6 of train_heads on given ROI-aligned features: the
+        HEAD_TRAINING stage's model (core/models.py:4044-4115), which takes
+        rois_aligned [B,T,P,P,P,C], mask_aligned [B,T,M,M,M,C], image_meta and
+        the three targets (target_class_ids [B,T] int32, target_bbox [B,T,6],
+        target_mask [B,T,m,m,m]) as inputs -- a HeadGenerator item, or
+        train_heads' own PyramidROIAlign results.  The features of a head that
+        is not selected may be None.  Returns train_heads' dictionary without
+        "rois"."""
+        from . import nn as mnn
+        from .head_losses import active_class_ids_from_meta, mrcnn_losses
+        from .optim import apply_max_norm
+        from .params import CHUNK
+        heads = MaskRCNN._check_heads(heads, "train_heads_on_features")
+        cls, msk = "classifier" in heads, "mask" in heads
+        if (cls and rois_aligned is None) or (msk and mask_aligned is None):
+            raise ValueError("train_heads_on_features: the features of a selected head are missing")
+        ops._dev(rois_aligned, mask_aligned, image_meta, target_class_ids, target_bbox, target_mask)
+        pooled, mpooled = rois_aligned, mask_aligned
         ranges = []
         if cls:
             pooled = pooled.detach().requires_grad_(True)
@@ -862,13 +888,75 @@ class MaskRCNN:
         optimizer.step(self.store, chunks=ranges[0])
         if cls:
             apply_max_norm(self.store, self.classifier.max_norm_constraints)
-        r = {"loss": total.detach(), "rois": rois, "target_class_ids": target_class_ids, "target_bbox": target_bbox,
+        r = {"loss": total.detach(), "target_class_ids": target_class_ids, "target_bbox": target_bbox,
              "target_mask": target_mask}
         if cls:
             r.update(mrcnn_class_loss=lc, mrcnn_bbox_loss=lb, d_pooled=pooled.grad)
         if msk:
             r.update(mrcnn_mask_loss=lm, d_mask_pooled=mpooled.grad)
         return r
+
+    @torch.no_grad()
+    def head_target_generation(self, dataset, output_dir, split, seed=0, image_ids=None):
+        """TARGET_GENERATION for one split (RPN.head_target_generation's
+        ``_run_split``, core/models.py:3638-3779): for each of the first
+        max(1, round(TARGET_RATIO * n)) images of ``image_ids`` (default: the
+        prepared ToyDataset's) --
+
+          * ``dataset.load_image(id, device=...)`` / ``load_data`` without
+            augmentation (the generator's MODE == "targeting" branch), the
+            image_meta with every class active;
+          * the trunk, proposals, DetectionTargetLayer (``_head_targets``; image
+            k of the split samples with seed + k) and the two PyramidROIAligns;
+          * an image with fewer than MIN_POSITIVE_TARGETS (default 25) positive
+            target class ids is skipped;
+          * ``m3d.headstore.save_head_targets``: float16 features and bit-packed
+            masks made on the device, the reference's six .npz files named by
+            the image file's basename without its extension;
+          * one row of paths in ``<output_dir>/datasets/<split>.csv``.
+
+        Returns {"processed", "saved", "skipped": [(name, positives), ...],
+        "csv"}.  The volume must have config.IMAGE_SHAPE (nothing is resized).
+        The reference's prints and its loop that swallows every exception are
+        not reproduced: an error raises."""
+        import os
+
+        from . import headstore
+        from .model import compose_image_meta
+        c = self.config
+        shape = tuple(int(v) for v in c.IMAGE_SHAPE)
+        ids = [int(i) for i in (dataset.image_ids if image_ids is None else image_ids)]
+        n = max(1, int(round(float(getattr(c, "TARGET_RATIO", 1.0)) * len(ids))))
+        min_positive = int(getattr(c, "MIN_POSITIVE_TARGETS", 25))
+        csv_path = headstore.write_csv_header(output_dir, split)
+        H, W, D = shape[:3]
+        processed = saved = 0
+        skipped = []
+        for k, image_id in enumerate(ids[:n]):
+            name = os.path.splitext(os.path.basename(str(dataset.image_info[image_id]["path"])))[0]
+            image = dataset.load_image(image_id, device=self.device)
+            if tuple(image.shape) != shape:
+                raise ValueError(f"image {image_id} has shape {tuple(image.shape)}, the model is built for {shape} "
+                                 "(head_target_generation does not resize)")
+            boxes, class_ids, masks = dataset.load_data(image_id)
+            meta = torch.from_numpy(compose_image_meta(image_id, shape, shape, (0, 0, 0, H, W, D), 1.0,
+                                                       np.ones(c.NUM_CLASSES, np.int32))[None]).to(self.device)
+            _, rois, _, tci, tbox, tmask, maps = self._head_targets(
+                image[None], meta, torch.from_numpy(np.asarray(class_ids, np.int32)[None]).to(self.device),
+                torch.from_numpy(np.asarray(boxes, np.float32).reshape(1, -1, 6)).to(self.device),
+                torch.from_numpy(np.ascontiguousarray(masks != 0)[None]).to(self.device), seed + k)
+            pooled = self.roi_align_classifier([rois, meta] + maps)
+            mpooled = self.roi_align_mask([rois, meta] + maps)
+            processed += 1
+            positives = int((tci > 0).sum())
+            if positives < min_positive:
+                skipped.append((name, positives))
+                continue
+            paths = headstore.save_head_targets(output_dir, name, rois[0], pooled[0], mpooled[0], tci[0], tbox[0],
+                                                tmask[0])
+            headstore.append_csv_row(csv_path, paths)
+            saved += 1
+        return {"processed": processed, "saved": saved, "skipped": skipped, "csv": csv_path}
 
     def load_weights(self, filepath, by_name=True, skip_mismatch=False, exclude=()):
         """keras_model.load_weights(filepath, by_name=True, ...) on the Keras-H5 format (m3d.weights)."""

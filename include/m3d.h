@@ -961,6 +961,48 @@ int m3d_flip_boxes(const float* in, int64_t N, int64_t H, int64_t W, int64_t D, 
                    m3d_stream_t s);
 
 /* ---------------------------------------------------------------------------
+ * Stored head targets: the narrow forms TARGET_GENERATION writes
+ * (RPN.head_target_generation, core/models.py:3585-3636: rois_aligned as
+ * float16, mask_aligned / target_mask bit-packed) made on the device, and
+ * their way back into a head-training batch (HeadGenerator.__getitem__,
+ * core/data_generators.py:385-412, 626-640).  Device pointers only; ordered on
+ * the caller's stream; nothing allocates or synchronises; every output element
+ * is written exactly once (no memset needed); all offsets are 64-bit.
+ * ------------------------------------------------------------------------- */
+/* np.packbits(x > 0.5) (_bitpack, core/models.py:3585-3595): bits[i] holds
+ * elements 8i .. 8i+7, the first in bit 7; a bit is set iff x > 0.5f (NaN and
+ * 0.5 give 0); the last byte is zero-filled when n % 8 != 0.  bits has
+ * (n + 7) / 8 bytes.  x must be 16-byte aligned.  n == 0: nothing is launched. */
+int m3d_pack_bits_f32(const float* x, int64_t n, uint8_t* bits, m3d_stream_t s);
+/* x.astype(np.float16) (core/models.py:3612): round to nearest even, overflow
+ * to +-inf, results in the half-subnormal range kept, -0 kept, NaN stays NaN
+ * (payload not pinned).  x must be 16-byte and h 8-byte aligned. */
+int m3d_f32_to_f16(const float* x, int64_t n, uint16_t* h, m3d_stream_t s);
+/* counts[r] = number of set bits among bits r*row_bits .. (r+1)*row_bits - 1 of
+ * a packed [rows, row_bits] array (a row need not start on a byte): count /
+ * row_bits is target_mask[i].mean() (core/data_generators.py:510-514) without
+ * unpacking.  Integer sums: the result does not depend on scheduling.  bits
+ * has (rows*row_bits + 7) / 8 bytes and must be 4-byte aligned; row_bits < 2^31. */
+int m3d_bits_row_counts(const uint8_t* bits, int64_t rows, int64_t row_bits, int32_t* counts, m3d_stream_t s);
+/* out[t,a,b,c,k] = src[sel[t], i0[a], i1[b], i2[c], k] as float32, out
+ * [T_out,M0,M1,M2,C], from a packed-bit (a bit becomes 0.0f / 1.0f) or a
+ * float16 (widened exactly) array of logical shape [R,S0,S1,S2,C]:
+ * _take_or_pad(_resize_spatial(x)) of core/data_generators.py:385-412, 626-640
+ * in one pass.  sel int32 [T_out]: a row with sel[t] < 0 is written as zeros
+ * (the padding); sel[t] >= R is the caller's error (the host validates sel
+ * before the call) and is written as zeros too, never read.  i0 / i1 / i2 are
+ * int32 device tables of lengths M0 / M1 / M2 (the identity, or
+ * np.linspace(0, S-1, M).astype(int64)); an entry outside [0, S) is clamped.
+ * out must be 16-byte aligned and a float16 source 8-byte aligned when
+ * C % 4 == 0 (4 and 2 otherwise).  T_out*M0*M1 and M2*C below 2^31. */
+int m3d_unpack_gather_bits(const uint8_t* bits, int64_t R, int64_t S0, int64_t S1, int64_t S2, int64_t C,
+                           const int32_t* sel, int64_t T_out, const int32_t* i0, const int32_t* i1,
+                           const int32_t* i2, int64_t M0, int64_t M1, int64_t M2, float* out, m3d_stream_t s);
+int m3d_unpack_gather_f16(const uint16_t* h, int64_t R, int64_t S0, int64_t S1, int64_t S2, int64_t C,
+                          const int32_t* sel, int64_t T_out, const int32_t* i0, const int32_t* i1,
+                          const int32_t* i2, int64_t M0, int64_t M1, int64_t M2, float* out, m3d_stream_t s);
+
+/* ---------------------------------------------------------------------------
  * Elementwise / reduction kernels of the backbone-FPN-RPN graph.
  * ------------------------------------------------------------------------- */
 /* KL.MaxPooling3D(k, strides, padding='same'|'valid') (core/models.py:245,3211);
