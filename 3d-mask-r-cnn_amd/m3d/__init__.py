@@ -12,6 +12,8 @@ Drop-in surface:
   m3d.headstore  the stored head targets of TARGET_GENERATION (core/models.py:3530-3796): float16 /
                bit-packed forms made and read back on the GPU; ToyHeadDataset (m3d.dataset),
                HeadGenerator (m3d.generator), MaskRCNN.head_target_generation / train_heads_on_features
+  m3d.rpn_eval   RPN_EVALUATION (core/utils.py:1251-1415): score_proposals (proposals against GT boxes on the
+               GPU), summarize (the callback's numbers on the host); RPN.evaluate (m3d.model) is the loop
   m3d.config   Config / load_config (core/config.py)
   m3d.parallel depth-slab sharding + RCCL gradient all-reduce
 All compute runs in libm3d.so (hand-written HIP for gfx950); there is no CPU

@@ -198,6 +198,8 @@ _SIGS = {
     "m3d_unmold_labels": [c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p],
     "m3d_label_pixelwise": [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p],
     "m3d_labels_stack": [c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p],
+    "m3d_rpn_eval_proposals": [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, ctypes.c_double, c_p, c_i64, c_p,
+                               c_p, c_p, c_p, c_p, c_p],
     "m3d_normalize_image_workspace_bytes": [c_i64, c_i64, c_i64, c_i32],
     "m3d_normalize_image": [c_p, c_i32, c_i64, c_i64, c_i64, c_i32, c_p, c_p, c_p, c_sz, c_p],
     "m3d_augment_image_workspace_bytes": [c_i64, c_i64, c_i64],

@@ -393,6 +393,66 @@ class RPN:
             return res
         return step
 
+    def evaluate(self, subsets, datasets, steps=None, seed=0):
+        """RPN_EVALUATION (RPN.evaluate, core/models.py:3799-3806, and the
+        callback after every epoch of RPN.train, 2165-2209 ->
+        core/utils.py:rpn_evaluation, 1251-1415): per subset the mean +- std
+        of the class and bbox loss, the share of GT boxes matched by one of the
+        first EVAL_TOPK_RPN proposals, their mean coordinate error, and
+        Detection@IoU@K over EVAL_MATCH_IOU_GRID x EVAL_TOPK_GRID.
+
+        ``subsets`` are names ("TRAIN SUBSET", "TEST SUBSET"; the result key is
+        the first word, lower-cased), ``datasets`` their datasets.  Per subset
+        an ``RPNGenerator(shuffle=False, seed=seed)`` serves min(``steps`` or
+        EVALUATION_STEPS, len(generator)) items; each item is
+        ``forward(proposals=True)`` and ``loss_total`` under no_grad, then
+        ``rpn_eval.score_proposals`` into the subset's device buffer, which
+        reaches the host in one synchronising copy at the subset's end ->
+        {subset: rpn_eval.summarize(...)}.
+
+        Differences from the reference: one image per item (IMAGES_PER_GPU > 1
+        raises in the generator).  The GT boxes are the pixel boxes of the item
+        actually served (``generator.last["boxes"]``: unjittered, after any
+        redraw or augmentation); the reference calls load_image_gt a second
+        time, and under AUGMENT that call draws fresh flips that no longer
+        belong to the predicted image.  Telemetry, the check_boxes prints and
+        the callback's round trip of the numbers through stdout and a regex
+        are not built."""
+        from . import rpn_eval
+        from .generator import RPNGenerator
+        cfg = self.config
+        shape = tuple(int(v) for v in cfg.IMAGE_SHAPE[:3])
+        topk, match_iou = int(getattr(cfg, "EVAL_TOPK_RPN", 10000)), float(getattr(cfg, "EVAL_MATCH_IOU", 0.50))
+        iou_grid = list(getattr(cfg, "EVAL_MATCH_IOU_GRID", [0.30, 0.40, 0.50]))
+        topk_grid = list(getattr(cfg, "EVAL_TOPK_GRID", [topk]))
+        T = len(iou_grid)
+        width = 2 + rpn_eval.record_len(rpn_eval.MAX_GT, T)       # two loss words, then the record
+        result = {}
+        for subset, dataset in zip(subsets, datasets):
+            gen = RPNGenerator(cfg, dataset, self.anchors.reshape(-1, 6), self.device, seed=seed, shuffle=False)
+            n = min(int(cfg.EVALUATION_STEPS if steps is None else steps), len(gen))
+            buf = torch.zeros((max(n, 1), width), device=self.device, dtype=torch.int32)
+            boxes_of, widest = [], 2
+            with torch.no_grad():
+                for k in range(n):
+                    image, targets = gen[k]
+                    out = self.forward(image, proposals=True)
+                    _, lc, lb = self.loss_total(out, targets)
+                    buf[k, :2].view(torch.float32).copy_(torch.stack([lc.reshape(()), lb.reshape(())]))
+                    boxes = np.asarray(gen.last["boxes"], np.float32).reshape(-1, 6)
+                    boxes_of.append(boxes)
+                    if len(boxes):
+                        rpn_eval.score_proposals(out["rpn_rois"], torch.from_numpy(boxes).to(self.device), shape,
+                                                 topk, match_iou, iou_grid, out=buf[k, 2:])
+                        widest = max(widest, 2 + rpn_eval.record_len(len(boxes), T))
+            host = buf[:n, :widest].cpu().numpy()                # the subset's one synchronising copy
+            losses = np.ascontiguousarray(host[:, :2]).view(np.float32)
+            records = [host[k, 2:] if len(b) else None for k, b in enumerate(boxes_of)]
+            key = subset.split()[0].lower()
+            result[key] = rpn_eval.summarize(records, losses[:, 0], losses[:, 1], boxes_of, topk_grid, iou_grid,
+                                             subset=key)
+        return result
+
     def load_weights(self, filepath, by_name=True, skip_mismatch=False, exclude=()):
         """keras_model.load_weights(filepath, by_name=True, ...) on the Keras-H5 format (m3d.weights)."""
         from .weights import load_weights

@@ -905,6 +905,40 @@ int m3d_label_pixelwise(const int32_t* labels, const uint8_t* gt_masks, int64_t 
 int m3d_labels_stack(const int32_t* labels, int64_t H, int64_t W, int64_t D, int64_t bytes_per_sample, void* stack,
                      m3d_stream_t s);
 
+/* RPN evaluation (RPN_EVALUATION): one image's proposals scored against its
+ * ground-truth boxes -- the per-image body of rpn_evaluation
+ * (core/utils.py:1289-1392) with compute_overlaps_3d (78-144) and denorm_boxes
+ * (1562-1574), restated in tests/rpnevalref.py.  rois [R,6] float32 normalised
+ * (y1,x1,z1,y2,x2,z2) as the ProposalLayer leaves them (zero-padded rows
+ * included), gt [G,6] float32 finite pixel boxes, grid [T] float32 thresholds.
+ *   pixel box of row j   float32(roi * (H,W,D,H,W,D)), columns 0..2 clamped to
+ *     [0,H] / [0,W] / [0,D] and 3..5 to [1,H] / [1,W] / [1,D] as min(max(x, lo),
+ *     hi); the row is valid when y2 > y1 && x2 > x1 && z2 > z1.  A NaN row is
+ *     invalid; a zero-padded row is the valid box (0,0,0,1,1,1), as there.
+ *   IoU, float32, in this order: both boxes corner-normalised; inter =
+ *     (max(y2i - y1i, 0) * max(x2i - x1i, 0)) * max(z2i - z1i, 0); vol =
+ *     ((y2 - y1) * (x2 - x1)) * (z2 - z1); union = max((vol_gt + vol_roi) -
+ *     inter, 1e-10f); iou = min(max(inter / union, 0), 1).
+ *   assoc [G] int32      the smallest valid row j < min(topk, R) whose first
+ *     maximum over g is g and whose (double) iou[g,j] > match_thr, else -1: the
+ *     reference's walk, in which each ROI claims its best GT box if that box
+ *     is unclaimed and the IoU passes.  The raw row index.
+ *   matched [G,6] float32  that row's pixel box; zeros where assoc[g] == -1.
+ *   first_hit [T,G] int32  the smallest valid row j < R with iou[g,j] >=
+ *     grid[t] (a float32 compare), else INT32_MAX: #{g: first_hit[t,g] < K} is
+ *     the hit count of any row prefix K.
+ *   counts [2] int32     the valid rows among the first min(topk, R), and the
+ *     smallest valid row of all R (INT32_MAX when none).
+ *   iou [G,R] float32    optional (may be NULL): every IoU, 0 for invalid j.
+ * Integer minima and counts only cross threads: the outputs do not depend on
+ * scheduling.  R may be 0 (rois may then be NULL); grid / first_hit may be NULL
+ * when T == 0.  M3D_EINVAL before any launch: other NULL pointers,
+ * non-positive H / W / D, negative R / topk / T, G outside [1, 512], T > 8,
+ * R * G beyond 31 bits. */
+int m3d_rpn_eval_proposals(const float* rois, int64_t R, const float* gt, int64_t G, int64_t H, int64_t W, int64_t D,
+                           int64_t topk, double match_thr, const float* grid, int64_t T, int32_t* assoc,
+                           float* matched, int32_t* first_hit, int32_t* counts, float* iou, m3d_stream_t s);
+
 /* The input pipeline: ToyDataset.load_image's normalisation
  * (core/data_generators.py:1603-1630: transpose, np.percentile [1, 99], clip,
  * mean / std, tanh(0.5 x)), the second normalisation of
