@@ -149,6 +149,9 @@ _SIGS = {
     "m3d_conv3d_rowsparse_scan_bytes": [c_i64],
     "m3d_conv3d_rowsparse_header_offset": [c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i64, c_i64, c_i32, c_i32],
     "m3d_conv3d_rowsparse_scan": [c_p, c_i64, c_i64, c_i32, c_p, c_sz, c_p],
+    "m3d_rpn_head_compact_workspace_bytes": [c_i64, c_i32, c_i32, c_i64, c_i64, c_i64],
+    "m3d_rpn_head_compact_bwd_data": [c_p, c_p],
+    "m3d_rpn_head_compact_bwd_weight": [c_p, c_p, c_p],
     "m3d_gemm_f32_ex": [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_p,
                         c_i32, c_i32, c_p],
     "m3d_splitk_reduce": [c_p, c_i32, c_i64, c_i64, c_p, c_p, c_p, c_i32, c_p, c_p],
@@ -259,6 +262,7 @@ _RESTYPES = {"m3d_last_error": ctypes.c_char_p, "m3d_nms3d_workspace_bytes": c_s
              "m3d_rpn_loss_workspace_bytes": c_sz, "m3d_head_loss_workspace_bytes": c_sz,
              "m3d_bn_act_bwd_workspace_bytes": c_sz, "m3d_bn_bwd_fused_workspace_bytes": c_sz, "m3d_conv3d_splitk_count": c_i32, "m3d_conv3d_wino_workspace_bytes": c_sz, "m3d_conv3d_wino_dgrad_workspace_bytes": c_sz, "m3d_conv3d_wino_v_bytes": c_sz,
              "m3d_conv3d_rowsparse_scan_bytes": c_sz, "m3d_conv3d_rowsparse_header_offset": c_sz,
+             "m3d_rpn_head_compact_workspace_bytes": c_sz,
              "m3d_conv3d_wino_u_bytes": c_sz, "m3d_conv3d_wino_tile_z": c_i32, "m3d_conv3d_wino_wgrad_tile_z": c_i32,
              "m3d_conv3d_wino_tile_y": c_i32, "m3d_conv3d_wino_dgrad_tile_y": c_i32,
              "m3d_conv3d_wino_dgrad_tile_z": c_i32, "m3d_col_sums_batched_workspace_bytes": c_sz,
@@ -298,6 +302,7 @@ def load(path: str = LIB_PATH):
 DET_ENTRY_POINTS = ("m3d_conv3d_bwd_weight", "m3d_conv3d_bwd_weight_halo", "m3d_conv3d_bwd_weight_wino",
                     "m3d_conv3d_bwd_weight_wino_u", "m3d_conv3d_bwd_weight_wino_ux", "m3d_conv3d_bwd_weight_wino_halo", "m3d_gemm_wgrad_f32",
                     "m3d_conv3d_bwd_weight_dil", "m3d_deconv3d_k2s2_bwd_weight",
+                    "m3d_rpn_head_compact_bwd_weight",
                     "m3d_sgd_keras", "m3d_adam_keras", "m3d_adadelta_keras")
 
 
@@ -320,6 +325,27 @@ class ColSumsItem(ctypes.Structure):
 
 
 COL_SUMS_MAX = 16          # M3D_COL_SUMS_MAX
+
+
+RPN_HEAD_MAX_LEVELS = 8    # M3D_RPN_HEAD_MAX_LEVELS
+RPN_HEAD_OVERFLOW_WORD = 16  # the sticky overflow word of the compact head backward's workspace (int32 index)
+
+
+class RpnHeadLevel(ctypes.Structure):
+    """m3d_rpn_head_level_t (include/m3d.h)."""
+    _fields_ = [("p", ctypes.c_void_p), ("s1", ctypes.c_void_p), ("s2", ctypes.c_void_p), ("dp", ctypes.c_void_p),
+                ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("D", ctypes.c_int32), ("accumulate", ctypes.c_int32)]
+
+
+class RpnHeadBwd(ctypes.Structure):
+    """m3d_rpn_head_bwd_t (include/m3d.h): the argument block of m3d_rpn_head_compact_bwd_data / _bwd_weight."""
+    _fields_ = [("nlevels", ctypes.c_int32), ("apl", ctypes.c_int32), ("cap", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("C0", ctypes.c_int64), ("C1", ctypes.c_int64), ("C2", ctypes.c_int64),
+                ("levels", RpnHeadLevel * RPN_HEAD_MAX_LEVELS), ("dlogits", ctypes.c_void_p),
+                ("dbbox", ctypes.c_void_p), ("w1", ctypes.c_void_p), ("w2", ctypes.c_void_p), ("w24", ctypes.c_void_p),
+                ("dw1", ctypes.c_void_p), ("db1", ctypes.c_void_p), ("dw2", ctypes.c_void_p), ("db2", ctypes.c_void_p),
+                ("dw24", ctypes.c_void_p), ("db24", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
+                ("ws_bytes", ctypes.c_size_t)]
 
 
 class _Lib:

@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import torch
 
+from . import _lib
 from .nn import BNFuse, GradLink, _RPNOut, conv_bn_act, conv_geom, max_pool3d, subsample221
 from .params import BNLayer, ConvLayer
 
@@ -182,8 +183,99 @@ class RPNHead:
         self.b_grad = None
         self.backbone = backbone        # its GradLinks / BNFuse records are checked in finish_backward
         self.fuse_records = []
+        # the caller's bound on the voxel rows the next forward's loss puts a gradient on (the targets know
+        # it: RPN.forward_backward); consumed by that forward.  None: no bound, the dense backward
+        self.active_rows_bound = None
+        self._compact_ws = {}           # (rows, cap, device) -> the compact route's zero-initialised workspace
+
+    def _compact_cap(self, feature_maps):
+        """cap of the compact backward (nn._RPNHeadCompact) for this forward, 0 for today's path."""
+        from . import nn, slab
+        bound, self.active_rows_bound = self.active_rows_bound, None
+        if (not nn.RPN_HEAD_COMPACT or nn.ROWSPARSE != 0 or bound is None or not torch.is_grad_enabled()
+                or slab.current() is not None or feature_maps[0].shape[0] != 1
+                or len(feature_maps) > _lib.RPN_HEAD_MAX_LEVELS
+                or not any(p.requires_grad for p in feature_maps)):
+            return 0
+        rows = sum(p.shape[1] * p.shape[2] * p.shape[3] for p in feature_maps)
+        cap = max(256, -(-int(bound) // 256) * 256)
+        return cap if rows >= nn.RPN_HEAD_COMPACT_MIN_ROWS and cap <= nn.RPN_HEAD_COMPACT_MAX_CAP else 0
+
+    def _w24(self):
+        apl, cin = self.apl, 256
+        w24 = torch.cat([self.cls.kernel.data.reshape(cin, 2 * apl),
+                         self.bbox.kernel.data.reshape(cin, 6 * apl)], dim=1).contiguous()
+        return w24, torch.cat([self.cls.bias.data, self.bbox.bias.data]).contiguous()
+
+    def forward_levels(self, feature_maps, need_dx=True):
+        """The three stages' forward launches without anything kept for a per-unit backward (the
+        compact route's forward, called with grad mode off): (s1, s2, logits, bbox, w24)."""
+        s1, s2 = [], []
+        wshare = {} if SHARE_WINO_WEIGHTS else None
+        for p in feature_maps:
+            g1 = conv_geom(tuple(p.shape[1:4]), (3, 3, 3), (1, 1, 1), "same")
+            s = conv_bn_act(p, self.shared1, g1, relu=True, need_dx=need_dx, wshare=wshare)
+            g2 = conv_geom(tuple(s.shape[1:4]), (1, 1, 1), (1, 1, 1), "valid")
+            s1.append(s)
+            s2.append(conv_bn_act(s, self.shared2, g2, relu=True, need_dx=need_dx))
+        w24, b24 = self._w24()
+        logits, bbox = _RPNOut.apply(w24, b24, None, self.apl, (), *s2)
+        return s1, s2, logits, bbox, w24
+
+    def _compact(self, feature_maps, cap):
+        from . import nn
+        dev = feature_maps[0].device
+        self.fuse_records = []
+        rows = sum(p.shape[1] * p.shape[2] * p.shape[3] for p in feature_maps)
+        L = _lib.load()
+        key = (rows, cap, dev)
+        if key not in self._compact_ws:
+            nb = int(L.m3d_rpn_head_compact_workspace_bytes(rows, cap, self.apl, feature_maps[0].shape[-1],
+                                                                 self.shared1.kernel.data.shape[-1],
+                                                                 self.shared2.kernel.data.shape[-1]))
+            if nb <= 0:
+                raise ValueError("rpn_head_compact: no workspace for these shapes")
+            # one workspace is held: before another shape's replaces it, its overflow word is read
+            # (a synchronising read, once per shape change), so no overflow is dropped unseen
+            if not torch.cuda.is_current_stream_capturing():
+                self.check_compact()
+            # zeroed once: the header's overflow word is sticky (check_compact)
+            self._compact_ws = {key: (torch.zeros(nb // 4 + 1, device=dev, dtype=torch.float32), nb)}
+        ws, wsb = self._compact_ws[key]
+        npad = -(-8 * self.apl // 32) * 32
+        self.w_grad = torch.zeros((256, npad), device=dev, dtype=torch.float32)
+        self.b_grad = torch.zeros((npad,), device=dev, dtype=torch.float32)
+        grads = []
+        for layer in (self.shared1, self.shared2):
+            g = layer.grad_dict(None)
+            if nn.GRAD_HOOK is not None:
+                nn.GRAD_HOOK.use(layer.name, [t for t in g.values() if t is not None])
+                g = dict(g, _hook=(nn.GRAD_HOOK, layer.name))
+            grads.append(g)
+        grads.append({"kernel": self.w_grad, "bias": self.b_grad})
+        logits, bbox = nn._RPNHeadCompact.apply(self, cap, ws, wsb, tuple(grads),
+                                                *[p.contiguous() for p in feature_maps])
+        return logits, torch.softmax(logits, dim=-1), bbox
+
+    def check_compact(self, wait=True):
+        """Raise if a compact backward found more active rows than its declared bound (its gradients
+        are NaN by construction): reads the sticky overflow word of the workspace, which synchronises
+        unless wait is False and the device is still busy.  Clears the word."""
+        for (rows, cap, dev), (ws, _) in self._compact_ws.items():
+            if not wait and not torch.cuda.current_stream(dev).query():
+                continue
+            word = ws[_lib.RPN_HEAD_OVERFLOW_WORD:_lib.RPN_HEAD_OVERFLOW_WORD + 1].view(torch.int32)
+            n = int(word.item())
+            if n:
+                word.zero_()
+                raise RuntimeError(f"rpn head: {n} backward pass(es) found more active voxel rows than the declared "
+                                   f"bound allows (cap {cap} of {rows} rows): their gradients are NaN; declare the "
+                                   "targets' true bound (RPNHead.active_rows_bound) or none")
 
     def __call__(self, feature_maps):
+        cap = self._compact_cap(feature_maps)
+        if cap:
+            return self._compact(feature_maps, cap)
         shared, fuses = [], []
         self.fuse_records = []
         # rpn_conv_shared1 is one kernel on every level: its Winograd weight
@@ -202,9 +294,7 @@ class RPNHead:
             wshare.pop("fwd", None)        # the forward's workspace is not needed past the loop
         apl = self.apl
         cin = 256
-        w24 = torch.cat([self.cls.kernel.data.reshape(cin, 2 * apl),
-                         self.bbox.kernel.data.reshape(cin, 6 * apl)], dim=1).contiguous()
-        b24 = torch.cat([self.cls.bias.data, self.bbox.bias.data]).contiguous()
+        w24, b24 = self._w24()
         grads = None
         self.w_grad = self.b_grad = None           # a new forward drops any unfinished head gradient
         if torch.is_grad_enabled():

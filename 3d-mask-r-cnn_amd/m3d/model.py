@@ -57,6 +57,9 @@ class RPNTargets:
         self.n_cls, self.n_pos = len(cls_idx), len(pos_idx)
         # K.mean denominators (global counts; a depth slab holds only part of the anchors)
         self.cls_denom, self.pos_denom = self.n_cls, self.n_pos
+        # the loss puts a gradient on the n_cls sampled anchors only, hence on at most as many voxel
+        # rows of the RPN head (backbone.RPNHead's compact backward; one volume only)
+        self.active_rows_bound = self.n_cls if B == 1 else None
         self._dense(flat, device)
 
     def _dense(self, flat_match, device):
@@ -92,6 +95,7 @@ class RPNTargets:
         t.gt_bbox = torch.from_numpy(rb[rows].reshape(-1, 6)).to(device)
         t.n_cls, t.n_pos = len(cls_idx), len(pos_idx)
         t.cls_denom, t.pos_denom = int((m != 0).sum()), len(gpos)
+        t.active_rows_bound = None
         t._dense(lm, device)
         return t
 
@@ -101,11 +105,15 @@ class DeviceRPNTargets:
     them inside the step): rpn_match int8 [A] and rpn_bbox [n, 6] (positives in
     anchor order).  The loss graphs' tf.where index sets become masks over all
     anchors and their counts stay on the device, so nothing waits for the host;
-    the sums run in a different order than the index-set form (same terms)."""
+    the sums run in a different order than the index-set form (same terms).
+    ``active_rows_bound``: the most anchors rpn_match can label (the builder
+    guarantees RPN_TRAIN_ANCHORS_PER_IMAGE); None, the default of hand-made
+    targets, declares nothing and the RPN head's backward stays dense."""
 
-    def __init__(self, rpn_match, rpn_bbox):
+    def __init__(self, rpn_match, rpn_bbox, active_rows_bound=None):
         self.match = rpn_match.reshape(-1)
         self.bbox = rpn_bbox.reshape(-1, 6)
+        self.active_rows_bound = active_rows_bound
 
 
 def _rpn_class_loss_device(t: DeviceRPNTargets, rpn_class_logits, alpha, gamma):
@@ -348,7 +356,11 @@ class RPN:
         """One step up to (not including) the optimizer: gradients in
         store.grad_flat, the ProposalLayer overlapped on its side stream."""
         self.store.zero_grad()
-        out = self.forward(image, proposals=False)
+        self.rpn.active_rows_bound = getattr(targets, "active_rows_bound", None)     # for this forward's head
+        try:
+            out = self.forward(image, proposals=False)
+        finally:
+            self.rpn.active_rows_bound = None        # (a forward that raised before the head leaves none armed)
         join = self.proposals_async(out)[1] if proposals and not PROPOSALS_AFTER_LOSS else None
         total, lc, lb = self.loss_total(out, targets)
         if proposals and PROPOSALS_AFTER_LOSS:

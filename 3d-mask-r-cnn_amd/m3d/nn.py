@@ -1684,3 +1684,93 @@ class _RPNOut(torch.autograd.Function):
             _log("conv1_bwd", 2 * f, 2 * f, 4.0 * (2 * nx + 2 * B * R * npad + 2 * w24.numel()), "bwd_data",
                  "rpn_class_raw+rpn_bbox_pred (wgrad+dgrad)", t0)
         return (None, None, None, None, None) + tuple(dshared)
+
+
+# The RPN head's backward on the sampled anchors' rows only (csrc/conv3d.hip,
+# m3d_rpn_head_compact_bwd_data / _bwd_weight): the active rows are
+# found once from the loss gradient and rpn_class_raw / rpn_bbox_pred,
+# rpn_conv_shared2 and rpn_conv_shared1 run their backward on compact [cap][C]
+# matrices, all pyramid levels at once.  backbone.RPNHead takes the route when
+# this is on, ROWSPARSE is 0, gradients are enabled, B = 1, no depth slab is
+# active, a bound <= 4096 on the active rows was declared for the forward (from
+# the targets: RPN.forward_backward) and the head has at least
+# RPN_HEAD_COMPACT_MIN_ROWS voxel rows; otherwise today's per-unit path.
+# The threshold: the head's backward alone (scripts/time_rpn_head_bwd.py, 1536
+# sampled anchors, dense -> compact, eager): 174592 rows (128^3) 2.63 -> 0.59 ms,
+# 21824 (64^3) 2.11 -> 0.52, 10912 (64 x 64 x 32) 2.05 -> 0.55, 5456 (64 x 64 x 16)
+# 2.12 -> 0.62 -- no crossover down to the smallest pyramid measured.  It stays
+# one row above 5456, the configuration whose launch plan
+# tests/golden/launch_plan.json pins on the per-unit path.
+RPN_HEAD_COMPACT = True
+RPN_HEAD_COMPACT_MIN_ROWS = 5457
+RPN_HEAD_COMPACT_MAX_CAP = 4096
+
+
+class _RPNHeadCompact(torch.autograd.Function):
+    """The RPN head's three stages of all pyramid levels as one function.  The
+    forward issues the units' forward launches (as in inference: no kept U, no
+    pre-BN output, no data-gradient weight transform); the backward issues the
+    compact launches and returns the levels' gradients.  Parameter gradients go
+    where the units write them (``grads``: rpn_conv_shared1's, rpn_conv_shared2's
+    and the head's padded class/bbox pair)."""
+
+    @staticmethod
+    def forward(ctx, head, cap, ws, wsb, grads, *fmaps):
+        # (grad mode is off in here: the units below record nothing and keep nothing)
+        s1, s2, logits, bbox, w24 = head.forward_levels(fmaps, need_dx=False)
+        ctx.save_for_backward(w24, *fmaps, *s1, *s2)
+        ctx.head, ctx.cap, ctx.ws, ctx.wsb, ctx.grads = head, cap, ws, wsb, grads
+        return logits, bbox
+
+    @staticmethod
+    def backward(ctx, dlogits, dbbox):
+        w24, *rest = ctx.saved_tensors
+        nl = len(rest) // 3
+        fmaps, s1, s2 = rest[:nl], rest[nl:2 * nl], rest[2 * nl:]
+        head, cap, ws, g1, g2, g24 = ctx.head, ctx.cap, ctx.ws, *ctx.grads
+        apl, dev = head.apl, fmaps[0].device
+        C0, C1, C2 = fmaps[0].shape[-1], s1[0].shape[-1], s2[0].shape[-1]
+        R = sum(p.shape[1] * p.shape[2] * p.shape[3] for p in fmaps)
+        dlogits = torch.zeros((1, R * apl, 2), device=dev) if dlogits is None else dlogits.contiguous()
+        dbbox = torch.zeros((1, R * apl, 6), device=dev) if dbbox is None else dbbox.contiguous()
+        dps = [torch.empty_like(p) for p in fmaps]
+        a = _lib.RpnHeadBwd()
+        a.nlevels, a.apl, a.cap, a.C0, a.C1, a.C2 = nl, apl, cap, C0, C1, C2
+        for l in range(nl):
+            lv = a.levels[l]
+            lv.p, lv.s1, lv.s2, lv.dp = ptr(fmaps[l]), ptr(s1[l]), ptr(s2[l]), ptr(dps[l])
+            lv.H, lv.W, lv.D = fmaps[l].shape[1:4]
+        a.dlogits, a.dbbox = ptr(dlogits), ptr(dbbox)
+        a.w1, a.w2, a.w24 = ptr(head.shared1.kernel.data), ptr(head.shared2.kernel.data), ptr(w24)
+        a.dw1, a.db1, a.dw2, a.db2 = ptr(g1["kernel"]), ptr(g1["bias"]), ptr(g2["kernel"]), ptr(g2["bias"])
+        a.dw24, a.db24 = ptr(g24["kernel"]), ptr(g24["bias"])
+        a.workspace, a.ws_bytes = ptr(ws), ctx.wsb
+        L = _L()
+        t0 = _span()
+        check(L.m3d_rpn_head_compact_bwd_data(ctypes.addressof(a), stream()), "rpn_head_compact_bwd_data")
+        n8 = 8 * apl
+        npad = -(-n8 // 32) * 32
+        nx = sum(p.numel() for p in fmaps)
+        if LAYER_LOG is not None:
+            # what runs: the products at cap rows; the scan of the loss gradient, the row -> slot map (written
+            # once, read by 27 taps), the compact operands, ct written and read, every level's dx written
+            f = 2.0 * cap * (n8 * C2 + C2 * C1 + C1 * 27 * C0)
+            nb = 4.0 * (R * n8 + 2 * R + 3 * cap * (npad + C1 + C2) + 2 * cap * 27 * C0 + nx) \
+                + 10.0 * (C1 * C2 + 27 * C0 * C1)
+            _log("rpn_head_compact", f, f, nb, "bwd_data", "rpn head (compact data gradient)", t0, "x3")
+        # the weight gradients on the side stream, after the data gradient (WGRAD_LAST)
+        side = _wgrad_stream(dev)
+        if side is not None:
+            ws.record_stream(side)
+            for p in fmaps:
+                p.record_stream(side)
+        with _on_side(side):
+            tw = _span()
+            check(L.m3d_rpn_head_compact_bwd_weight(ctypes.addressof(a), stream()), "rpn_head_compact_bwd_weight")
+            if LAYER_LOG is not None:
+                f = 2.0 * cap * (npad * C2 + C2 * C1 + C1 * 27 * C0)
+                nb = 4.0 * (cap * (npad + C1 + 2 * C2 + C1) + 3 * 27 * cap * C0 + 2 * (C2 * npad + C1 * C2 + 27 * C0 * C1))
+                _log("rpn_head_compact", f, f, nb, "bwd_weight", "rpn head (compact weight gradients)", tw, "x3")
+        _grad_done(g2, side)
+        _grad_done(g1, side)
+        return (None,) * 5 + tuple(dps)

@@ -210,7 +210,11 @@ def data_parallel_train_step(model, image, targets, world, proposals=True, overl
         hook.reset()
         mnn.GRAD_HOOK = hook
     try:
-        out = model.forward(image, proposals=False)
+        model.rpn.active_rows_bound = getattr(targets, "active_rows_bound", None)
+        try:
+            out = model.forward(image, proposals=False)
+        finally:
+            model.rpn.active_rows_bound = None
         join = model.proposals_async(out)[1] if proposals else None   # overlaps the backward
         total, lc, lb = model.loss_total(out, targets)
         total.backward()

@@ -209,4 +209,4 @@ class RPNTargetBuilder:
             self._flag_host.copy_(self.counts, non_blocking=True)
             self._flag_event = torch.cuda.Event()
             self._flag_event.record()
-        return DeviceRPNTargets(self.match, self.bbox)
+        return DeviceRPNTargets(self.match, self.bbox, active_rows_bound=self.total)

@@ -427,6 +427,73 @@ size_t m3d_conv3d_rowsparse_header_offset(int64_t B, int64_t H, int64_t W, int64
                                           int64_t Cin, int64_t Cout, int32_t pass, int32_t tile_y);
 int m3d_conv3d_rowsparse_scan(const float* dz, int64_t rows, int64_t C, int32_t cap, void* ws, size_t ws_bytes,
                               m3d_stream_t s);
+/* RPN head backward on the sampled anchors' rows (B = 1).  The head
+ * (core/models.py:512-557) is rpn_conv_shared1 (3x3x3, C0 -> C1, ReLU),
+ * rpn_conv_shared2 (1x1x1, C1 -> C2, ReLU) and rpn_class_raw / rpn_bbox_pred
+ * (1x1x1, C2 -> 2 apl / 6 apl), applied to every pyramid level; the RPN loss
+ * leaves a gradient on the sampled anchors only, so the gradient is row-sparse
+ * down to the 3x3x3 conv.  The two entry points run the whole head's backward
+ * over the active voxel rows of all levels at once:
+ * m3d_rpn_head_compact_bwd_data scans dlogits [R][2 apl] / dbbox [R][6 apl]
+ * (R = the levels' rows concatenated; a row is active if any element is
+ * != 0.0f, so -0.0f is not and a NaN is), gathers the n active rows of the
+ * gradient and of each level's s1 / s2 into compact [cap][C] matrices (rows
+ * n..cap zero), runs the 1x1x1 chain on them (db24, db2, db1 += the column
+ * sums, in a fixed order; the ReLU masks are s2 > 0 and s1 > 0) and writes each
+ * level's dp (accumulate 0: voxels without an active neighbour are zero-filled;
+ * 1: added to, the others untouched).  m3d_rpn_head_compact_bwd_weight,
+ * enqueued after it (the same stream, or one that waits for it), adds the three
+ * weight gradients from the compact matrices left in the workspace: dw24
+ * [C2][npad] (npad = 8 apl rounded up to 32; column j < 2 apl is
+ * rpn_class_raw's, the next 6 apl rpn_bbox_pred's) and dw2 [C1][C2] (both
+ * summed in double in a fixed order), and dw1 [27][C0][C1] (a split GEMM
+ * honouring det as m3d_conv3d_bwd_weight_wino_ux).  The two 1x1x1 data
+ * products keep double running sums and round once; rpn_conv_shared1's run on
+ * the split GEMMs.  w24 is [C2][8 apl] in the same column order; w2 must be
+ * 16-byte aligned.
+ * Everything is decided on the device with launch shapes fixed by (R, cap): no
+ * host read-back, graph-replay safe.  cap, a multiple of 256 in [256, 4096],
+ * is the caller's bound on n.  There is no dense fallback: when the device
+ * finds n > cap it adds one to the sticky int32 word [16] of the workspace
+ * (the caller clears it; a workspace must start zeroed) and fills the compact
+ * gradient with NaN, so every gradient of the step becomes NaN rather than a
+ * silently truncated one.  The workspace
+ * (m3d_rpn_head_compact_workspace_bytes; 0 for invalid arguments) starts with
+ * the header of m3d_conv3d_rowsparse_scan for R rows (state 2, n at [3] clamped
+ * to cap; the raw n at [8], the overflow word at [16], the first compact slot
+ * of level l at [32 + l], l = 0..nlevels); it carries the compact matrices from
+ * the data call to the weight call. */
+#define M3D_RPN_HEAD_MAX_LEVELS 8
+typedef struct m3d_rpn_head_level {
+    const float* p;     /* rpn_conv_shared1's input [H][W][D][C0] */
+    const float* s1;    /* rpn_conv_shared1's output [H][W][D][C1] */
+    const float* s2;    /* rpn_conv_shared2's output [H][W][D][C2] */
+    float* dp;          /* the gradient of p (data call) */
+    int32_t H, W, D;
+    int32_t accumulate;
+} m3d_rpn_head_level_t;
+typedef struct m3d_rpn_head_bwd {
+    int32_t nlevels, apl, cap, reserved;
+    int64_t C0, C1, C2;
+    m3d_rpn_head_level_t levels[M3D_RPN_HEAD_MAX_LEVELS];
+    const float* dlogits;
+    const float* dbbox;
+    const float* w1;    /* [3][3][3][C0][C1] */
+    const float* w2;    /* [C1][C2] */
+    const float* w24;   /* [C2][8 apl] */
+    float* dw1;
+    float* db1;
+    float* dw2;
+    float* db2;
+    float* dw24;        /* [C2][npad] */
+    float* db24;        /* [npad] */
+    void* workspace;
+    size_t ws_bytes;
+} m3d_rpn_head_bwd_t;
+size_t m3d_rpn_head_compact_workspace_bytes(int64_t rows, int32_t cap, int32_t apl, int64_t C0, int64_t C1,
+                                            int64_t C2);
+int m3d_rpn_head_compact_bwd_data(const m3d_rpn_head_bwd_t* a, m3d_stream_t s);
+int m3d_rpn_head_compact_bwd_weight(const m3d_rpn_head_bwd_t* a, const m3d_det_t* det, m3d_stream_t s);
 /* Depth-slab forms (multi-GPU sharding of one volume, m3d/slab.py): x is this
  * rank's slab [B,H,W,Dl,C] and x_halo [B,H,W,2,C] the neighbours' boundary
  * planes (plane 0 = z -1 from the lower rank, valid if has_lo; plane 1 = z Dl

@@ -59,6 +59,8 @@ def main():
             mnn.RELU_CAPTURE = {}
             with deterministic():
                 try:
+                    # the step's route: the targets' bound on the active rows (the compact RPN-head backward)
+                    model.rpn.active_rows_bound = RPNTargets(match, bbox, dev).active_rows_bound
                     out = model.forward(image.to(dev), proposals=False)
                     masks = mnn.RELU_CAPTURE
                 finally:
