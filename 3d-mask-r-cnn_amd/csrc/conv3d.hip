@@ -24,7 +24,7 @@
 // + residual (same shape or (2,2,1)-upsampled FPN source), ReLU, strided /
 // channel-split stores (RPN class|bbox heads write their concatenated outputs
 // directly).
-#include "common.h"
+#include "conv_types.h"
 #include <stdlib.h>
 
 namespace m3d {
@@ -148,15 +148,7 @@ __device__ __forceinline__ float f4get(const float4& v, int i) {
 // of the f32 FMA itself.  v_mfma_f32_32x32x16_bf16 retires 16x the FLOPs per
 // cycle of v_mfma_f32_32x32x2_f32, so 6 of them are 2.7x the f32 MFMA rate.
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ uint32_t bf16_bits(float x) {
-    return (uint32_t)__builtin_bit_cast(unsigned short, (__bf16)x);
-}
-__device__ __forceinline__ void split3(float x, uint32_t& h, uint32_t& m, uint32_t& l) {
-    h = bf16_bits(x);
-    const float r = x - __uint_as_float(h << 16);
-    m = bf16_bits(r);
-    l = bf16_bits(r - __uint_as_float(m << 16));
-}
+// (bf16_bits / split3: conv_types.h)
 // float4 (4 consecutive k) -> three 4 x bf16 packets (element j at bits 16j).
 // Two elements per conversion (v_cvt_pk_bf16_f32 with two sources) and per
 // subtraction (v_pk_add_f32): 20 VALU per float4 instead of 41 for four
@@ -1831,9 +1823,8 @@ static int launch_wgrad_tr(const float* A, const float* Bm, float* C, int64_t M,
 // fresh: C is uninitialised scratch (nbatch contiguous items, bsc = K * N) and
 // the result is C[b] = A[b]^T B[b]: owner store or zero-fill, see wg_settle.
 // Returns 0, or the hipError_t of a failed zero-fill (fresh only).
-static int launch_wgrad_x3(const float* A, const float* Bm, float* C, int64_t M, int K, int N, int nbatch,
-                           int64_t bsa, int64_t bsb, int64_t bsc, hipStream_t s, bool fresh = false,
-                           const int* gate = nullptr) {
+int launch_wgrad_x3(const float* A, const float* Bm, float* C, int64_t M, int K, int N, int nbatch, int64_t bsa,
+                    int64_t bsb, int64_t bsc, hipStream_t s, bool fresh, const int* gate) {
     if (K >= 192 && N >= 192)
         return launch_wgrad_tr(A, Bm, C, M, K, N, nbatch, bsa, bsb, bsc, s, fresh, gate);
     if (K <= 64 || N <= 64) {          // x3_wgrad64_kernel: 64x64 tiles, the m chunk over the waves
@@ -3824,35 +3815,6 @@ extern "C" int m3d_conv3d_fwd(const float* x, int64_t B, int64_t H, int64_t W, i
                               y, ldy, y2, ldy2, split_n, s);
 }
 
-static int bwd_data_direct(const float* dz, const float* w, int64_t B, int64_t H, int64_t W, int64_t D, int64_t Cin,
-                           int32_t kh, int32_t kw, int32_t kd, int64_t Cout, int64_t OH, int64_t OW, int64_t OD,
-                           int32_t sy, int32_t sx, int32_t sz, int32_t py, int32_t px, int32_t pz, float* dx,
-                           int32_t accumulate, hipStream_t s, const Epi* fb, int64_t* fb_rows, int32_t dly = 1,
-                           int32_t dlx = 1, int32_t dlz = 1);
-
-extern "C" int m3d_conv3d_bwd_data(const float* dz, const float* w, int64_t B, int64_t H,
-                                   int64_t W, int64_t D, int64_t Cin, int32_t kh, int32_t kw,
-                                   int32_t kd, int64_t Cout, int64_t OH, int64_t OW, int64_t OD,
-                                   int32_t sy, int32_t sx, int32_t sz, int32_t py, int32_t px,
-                                   int32_t pz, float* dx, int32_t accumulate, m3d_stream_t s) {
-    return bwd_data_direct(dz, w, B, H, W, D, Cin, kh, kw, kd, Cout, OH, OW, OD, sy, sx, sz, py, px, pz, dx,
-                           accumulate, st(s), nullptr, nullptr);
-}
-
-// The data gradient of a stride-1 dilated conv (mrcnn_mask_conv3b, core/models.py:1215-1218): the
-// same implicit GEMM over dz on the flipped taps, stepped by the dilation, with pad' = dl*(k-1) - pad.
-extern "C" int m3d_conv3d_bwd_data_dil(const float* dz, const float* w, int64_t B, int64_t H, int64_t W,
-                                       int64_t D, int64_t Cin, int32_t kh, int32_t kw, int32_t kd,
-                                       int64_t Cout, int64_t OH, int64_t OW, int64_t OD, int32_t sy,
-                                       int32_t sx, int32_t sz, int32_t py, int32_t px, int32_t pz,
-                                       int32_t dly, int32_t dlx, int32_t dlz, float* dx,
-                                       int32_t accumulate, m3d_stream_t s) {
-    if (sy != 1 || sx != 1 || sz != 1) return einval("conv3d bwd-data (dilated): stride must be 1");
-    if (accumulate != 0 && accumulate != 1) return einval("conv3d bwd-data (dilated): accumulate must be 0 or 1");
-    return bwd_data_direct(dz, w, B, H, W, D, Cin, kh, kw, kd, Cout, OH, OW, OD, sy, sx, sz, py, px, pz, dx,
-                           accumulate, st(s), nullptr, nullptr, dly, dlx, dlz);
-}
-
 // the output-tile height dispatch_gemm picks for a GEMM of N columns (rows of
 // the fused BN backward's channel partials: one per tile row)
 static int dispatch_bm(const ConvP& p, int nbatch = 1) {
@@ -3864,8 +3826,8 @@ static int dispatch_bm(const ConvP& p, int nbatch = 1) {
 static int bwd_data_direct(const float* dz, const float* w, int64_t B, int64_t H, int64_t W, int64_t D, int64_t Cin,
                            int32_t kh, int32_t kw, int32_t kd, int64_t Cout, int64_t OH, int64_t OW, int64_t OD,
                            int32_t sy, int32_t sx, int32_t sz, int32_t py, int32_t px, int32_t pz, float* dx,
-                           int32_t accumulate, hipStream_t hs, const Epi* fb, int64_t* fb_rows, int32_t dly,
-                           int32_t dlx, int32_t dlz) {
+                           int32_t accumulate, hipStream_t hs, const Epi* fb, int64_t* fb_rows, int32_t dly = 1,
+                           int32_t dlx = 1, int32_t dlz = 1) {
     int rc = conv_check(B, H, W, D, Cin, kh, kw, kd, Cout, OH, OW, OD, sy, sx, sz);
     if (rc) return rc;
     if (dly <= 0 || dlx <= 0 || dlz <= 0) return einval("conv3d bwd-data: dilation must be positive");
@@ -3929,6 +3891,29 @@ static int bwd_data_direct(const float* dz, const float* w, int64_t B, int64_t H
     }
     dispatch_gemm<true, true>(p, e, hs);
     return check_launch("conv_gemm_kernel(bwd-data)");
+}
+
+extern "C" int m3d_conv3d_bwd_data(const float* dz, const float* w, int64_t B, int64_t H,
+                                   int64_t W, int64_t D, int64_t Cin, int32_t kh, int32_t kw,
+                                   int32_t kd, int64_t Cout, int64_t OH, int64_t OW, int64_t OD,
+                                   int32_t sy, int32_t sx, int32_t sz, int32_t py, int32_t px,
+                                   int32_t pz, float* dx, int32_t accumulate, m3d_stream_t s) {
+    return bwd_data_direct(dz, w, B, H, W, D, Cin, kh, kw, kd, Cout, OH, OW, OD, sy, sx, sz, py, px, pz, dx,
+                           accumulate, st(s), nullptr, nullptr);
+}
+
+// The data gradient of a stride-1 dilated conv (mrcnn_mask_conv3b, core/models.py:1215-1218): the
+// same implicit GEMM over dz on the flipped taps, stepped by the dilation, with pad' = dl*(k-1) - pad.
+extern "C" int m3d_conv3d_bwd_data_dil(const float* dz, const float* w, int64_t B, int64_t H, int64_t W,
+                                       int64_t D, int64_t Cin, int32_t kh, int32_t kw, int32_t kd,
+                                       int64_t Cout, int64_t OH, int64_t OW, int64_t OD, int32_t sy,
+                                       int32_t sx, int32_t sz, int32_t py, int32_t px, int32_t pz,
+                                       int32_t dly, int32_t dlx, int32_t dlz, float* dx,
+                                       int32_t accumulate, m3d_stream_t s) {
+    if (sy != 1 || sx != 1 || sz != 1) return einval("conv3d bwd-data (dilated): stride must be 1");
+    if (accumulate != 0 && accumulate != 1) return einval("conv3d bwd-data (dilated): accumulate must be 0 or 1");
+    return bwd_data_direct(dz, w, B, H, W, D, Cin, kh, kw, kd, Cout, OH, OW, OD, sy, sx, sz, py, px, pz, dx,
+                           accumulate, st(s), nullptr, nullptr, dly, dlx, dlz);
 }
 
 // ---- data gradients with the fused BN-ReLU backward of the producing unit -----
@@ -4334,9 +4319,6 @@ static int wino_check(int64_t B, int64_t H, int64_t W, int64_t D, int64_t OD, in
 static bool wino_per_item(int64_t B, int64_t H, int64_t W, int64_t D, int64_t OD, int64_t Cin, int64_t Cout) {
     return per_item(B, H * W * (D > OD ? D : OD), Cin > Cout ? Cin : Cout, 0, 0);
 }
-// Workspace: V [P][Cin][Cout] + U [P][T][C1] + M [P][T][C2] (P = 16*(NZ+2) points) with
-// {C1, C2} = {Cin, Cout} (fwd / wgrad) or {Cout, Cin} (bwd-data), T the larger
-// of the fwd (tiles over OD) and bwd-data (tiles over D) tile counts.
 // launch the NZ = 4 instantiation of a Winograd transform kernel
 #define WINO_LAUNCH(kern, ...) hipLaunchKernelGGL(kern<WNZ>, __VA_ARGS__)
 
@@ -4346,44 +4328,54 @@ extern "C" int32_t m3d_conv3d_wino_tile_y(void) { return WNY; }
 extern "C" int32_t m3d_conv3d_wino_dgrad_tile_y(void) { return wino_dgrad_ny(); }
 extern "C" int32_t m3d_conv3d_wino_dgrad_tile_z(void) { return WNZ; }
 
-// the row-sparse header behind a call's layout (rs_hdr, below) for dz of `rows` voxel rows
-static size_t rs_hdr_bytes(int64_t rows);
-
-extern "C" size_t m3d_conv3d_wino_workspace_bytes(int64_t B, int64_t H, int64_t W, int64_t D,
-                                                  int64_t OD, int64_t Cin, int64_t Cout) {
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    if (wino_per_item(B, H, W, D, OD, Cin, Cout)) B = 1;     // run one batch item at a time
-    size_t best = 0;
-    // the data gradient's y tile is a per-call argument (m3d_conv3d_bwd_data_wino_vy / _bny): both sizes
-    for (const int ny : {2, 4}) {
-        const WinoGeom g = wino_geom(B, H, W, D > OD ? D : OD, D, 1, ny);
-        const size_t P = (size_t)wino_points(ny);
-        const size_t eb = 6;                          // V holds three bf16 planes; U is laid out alike
-        const size_t wt = al(sizeof(float) * 27 * (size_t)Cin * Cout);
-        // U (eb bytes / element) then M (fp32), in either role order (fwd: U over
-        // Cin, M over Cout; bwd-data: the reverse)
-        const size_t um1 = al(eb * P * (size_t)g.T * Cin) + al(4 * P * (size_t)g.T * Cout);
-        const size_t um2 = al(eb * P * (size_t)g.T * Cout) + al(4 * P * (size_t)g.T * Cin);
-        const size_t b = wt + al(eb * P * (size_t)Cin * Cout) + (um1 > um2 ? um1 : um2);
-        best = b > best ? b : best;
-    }
-    return best + rs_hdr_bytes(B * H * W * (D > OD ? D : OD));
-}
-
-struct WinoWs { float *V, *U, *M, *WT; };
-// bytes wino_ws lays out for geometry g, operand widths C1 (U) / C2 (M) and the y tile;
-// the row-sparse header follows at this offset
-static size_t wino_ws_layout(const WinoGeom& g, int64_t C1, int64_t C2, int ny) {
+// One call's workspace, every region 256-byte aligned:
+//   [WT: the transposed kernel, fp32 27 C1 C2][V: P C1 C2][U: P T C1][M: P T C2, fp32]
+// V and U at 6 bytes per element (three bf16 planes; a fp32 U uses 4 of them),
+// C1 / C2 the widths of U / M: {Cin, Cout} for the forward and the weight
+// gradient, {Cout, Cin} for the data gradient, P the points of the y tile.
+// The row-sparse header (rs_hdr) follows at `total`.
+struct WinoLayout { size_t v, u, m, total; };      // byte offsets (WT at 0)
+static WinoLayout wino_layout(const WinoGeom& g, int64_t C1, int64_t C2, int ny) {
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t P = (size_t)wino_points(ny);
     const size_t eb = 6;
-    const size_t wt = al(sizeof(float) * 27 * (size_t)C1 * C2);
-    return wt + al(eb * P * (size_t)C1 * C2) + al(eb * P * (size_t)g.T * C1) + al(4 * P * (size_t)g.T * C2);
+    WinoLayout l{};
+    l.v = al(sizeof(float) * 27 * (size_t)C1 * C2);
+    l.u = l.v + al(eb * P * (size_t)C1 * C2);
+    l.m = l.u + al(eb * P * (size_t)g.T * C1);
+    l.total = l.m + al(4 * P * (size_t)g.T * C2);
+    return l;
 }
-// what a data-gradient call checks: its layout and the header for dz rows of depth max(D, OD)
+// what a call checks: its layout and the header for dz rows of depth max(D, OD)
 static size_t wino_ws_need(const WinoGeom& g, int64_t C1, int64_t C2, int ny) {
-    return wino_ws_layout(g, C1, C2, ny) + rs_hdr_bytes((int64_t)g.B * g.H * g.W * (g.D > g.Din ? g.D : g.Din));
+    return wino_layout(g, C1, C2, ny).total + rs_hdr_bytes((int64_t)g.B * g.H * g.W * (g.D > g.Din ? g.D : g.Din));
 }
+struct WinoWs { float *V, *U, *M, *WT; };
+static WinoWs wino_ws(void* ws, const WinoLayout& l) {
+    char* p = (char*)ws;
+    WinoWs w{};
+    w.WT = (float*)p;
+    w.V = (float*)(p + l.v);
+    w.U = (float*)(p + l.u);
+    w.M = (float*)(p + l.m);
+    return w;
+}
+
+// The one allocation every Winograd call of a layer fits: the largest layout over
+// the data gradient's y tiles (a per-call argument of m3d_conv3d_bwd_data_wino_vy
+// / _bny) and both role orders (fwd: U over Cin, M over Cout; bwd-data: the reverse)
+extern "C" size_t m3d_conv3d_wino_workspace_bytes(int64_t B, int64_t H, int64_t W, int64_t D,
+                                                  int64_t OD, int64_t Cin, int64_t Cout) {
+    if (wino_per_item(B, H, W, D, OD, Cin, Cout)) B = 1;     // run one batch item at a time
+    size_t best = 0;
+    for (const int ny : {2, 4}) {
+        const WinoGeom g = wino_geom(B, H, W, D > OD ? D : OD, D, 1, ny);
+        const size_t b1 = wino_ws_need(g, Cin, Cout, ny), b2 = wino_ws_need(g, Cout, Cin, ny);
+        best = std::max(best, std::max(b1, b2));
+    }
+    return best;
+}
+
 // the data gradient's own workspace at tile_y (0: the library default): the
 // layout bwd_data_wino checks (dz transformed over Cout, dx's points over Cin)
 extern "C" size_t m3d_conv3d_wino_dgrad_workspace_bytes(int64_t B, int64_t H, int64_t W, int64_t D, int64_t OD,
@@ -4392,19 +4384,6 @@ extern "C" size_t m3d_conv3d_wino_dgrad_workspace_bytes(int64_t B, int64_t H, in
     if (wino_per_item(B, H, W, D, OD, Cin, Cout)) B = 1;
     const int ny = tile_y ? tile_y : wino_dgrad_ny();
     return wino_ws_need(wino_geom(B, H, W, D, OD, 1, ny), Cout, Cin, ny);
-}
-// [WT: the transposed kernel][V][U][M]
-static WinoWs wino_ws(void* ws, const WinoGeom& g, int64_t Cin, int64_t Cout, int ny = WNY) {
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t P = (size_t)wino_points(ny);
-    char* p = (char*)ws;
-    WinoWs w{};
-    w.WT = (float*)p; p += al(sizeof(float) * 27 * (size_t)Cin * Cout);
-    const size_t eb = 6;
-    w.V = (float*)p; p += al(eb * P * (size_t)Cin * Cout);
-    w.U = (float*)p; p += al(eb * P * (size_t)g.T * Cin);
-    w.M = (float*)p;
-    return w;
 }
 
 // the input transform (U in fp32), reading a depth slab's halo planes when g.halo is set
@@ -4416,14 +4395,14 @@ static WinoWs wino_ws(void* ws, const WinoGeom& g, int64_t Cin, int64_t Cout, in
 
 // the P point GEMMs M[xi] = U[xi] V[xi] on split planes (U: T x K, V: N x K);
 // af32: U is fp32 [P][T][K] (split in the GEMM's LDS store)
-static void wino_gemm_x3(const WinoWs& ws, int64_t T, int K, int N, int P, hipStream_t s,
-                         bool af32 = false, const int* gate = nullptr, const int* mlim = nullptr) {
+void m3d::launch_gemm_x3(const float* U, const float* V, float* Mo, int64_t T, int K, int N, int P, hipStream_t s,
+                         bool af32, const int* gate, const int* mlim) {
     X3G q{};                   // (value-initialised: q.ep.on = 0, the plain C store)
     q.gate = gate; q.mlim = mlim;
-    q.a = reinterpret_cast<const unsigned short*>(ws.U);
-    q.af = ws.U;
-    q.b = reinterpret_cast<const unsigned short*>(ws.V);
-    q.c = ws.M;
+    q.a = reinterpret_cast<const unsigned short*>(U);
+    q.af = U;
+    q.b = reinterpret_cast<const unsigned short*>(V);
+    q.c = Mo;
     q.M = T; q.K = K; q.N = N; q.nbatch = P;
     q.psa = (int64_t)P * T * K; q.psb = (int64_t)P * K * N;
     q.bsa = T * K; q.bsb = (int64_t)K * N; q.bsc = T * N;
@@ -4460,10 +4439,13 @@ __global__ __launch_bounds__(256) void split3_kernel(const float* __restrict__ x
     x3[2 * n + i] = (unsigned short)l;
 }
 
+void m3d::launch_split3(const float* x, int64_t n, unsigned short* x3, hipStream_t s) {
+    hipLaunchKernelGGL(split3_kernel, dim3(grid_for(n, 256)), dim3(256), 0, s, x, n, x3);
+}
+
 extern "C" int m3d_split3_f32(const float* x, int64_t n, uint16_t* x3, m3d_stream_t s) {
     if (n <= 0) return einval("split3: n must be positive");
-    hipLaunchKernelGGL(split3_kernel, dim3(grid_for(n, 256)), dim3(256), 0, st(s), x, n,
-                       reinterpret_cast<unsigned short*>(x3));
+    launch_split3(x, n, reinterpret_cast<unsigned short*>(x3), st(s));
     return check_launch("split3_kernel");
 }
 
@@ -4473,12 +4455,8 @@ extern "C" int m3d_gemm_x3(const uint16_t* A3, const uint16_t* B3, float* C, int
     if (K % 32 || N % 4) return einval("gemm_x3: K must be a multiple of 32 and N of 4");
     if (M > 0x7FFFFFFF || M * K * 2 >= 0xFFFFFFF0LL || N * K * 2 >= 0xFFFFFFF0LL || M * N * 4 >= 0xFFFFFFF0LL)
         return einval("gemm_x3: operand larger than 4 GiB (32-bit buffer offsets)");
-    WinoWs ws{};
-    ws.U = (float*)const_cast<uint16_t*>(A3);
-    ws.V = (float*)const_cast<uint16_t*>(B3);
-    ws.M = C;
-    ws.WT = nullptr;
-    wino_gemm_x3(ws, M, (int)K, (int)N, (int)batch, st(s));
+    launch_gemm_x3(reinterpret_cast<const float*>(A3), reinterpret_cast<const float*>(B3), C, M, (int)K, (int)N,
+                   (int)batch, st(s));
     return check_launch("m3d_gemm_x3");
 }
 
@@ -4489,12 +4467,7 @@ extern "C" int m3d_gemm_x3_af(const float* A, const uint16_t* B3, float* C, int6
     if (!A || !B3 || !C) return einval("gemm_x3_af: null operand");
     if (M > 0x7FFFFFFF || M * K * 4 >= 0xFFFFFFF0LL || N * K * 2 >= 0xFFFFFFF0LL || M * N * 4 >= 0xFFFFFFF0LL)
         return einval("gemm_x3_af: operand larger than 4 GiB (32-bit buffer offsets)");
-    WinoWs ws{};
-    ws.U = const_cast<float*>(A);
-    ws.V = (float*)const_cast<uint16_t*>(B3);
-    ws.M = C;
-    ws.WT = nullptr;
-    wino_gemm_x3(ws, M, (int)K, (int)N, (int)batch, st(s), true);
+    launch_gemm_x3(A, reinterpret_cast<const float*>(B3), C, M, (int)K, (int)N, (int)batch, st(s), true);
     return check_launch("m3d_gemm_x3_af");
 }
 
@@ -4704,7 +4677,7 @@ static int fwd_wino(const float* x, int64_t B, int64_t H, int64_t W, int64_t D, 
     }
     WinoGeom g = wino_geom(B, H, W, OD, D, pz);
     g.halo = halo; g.hlo = hlo; g.hhi = hhi;
-    WinoWs ws = wino_ws(workspace, g, Cin, Cout);
+    WinoWs ws = wino_ws(workspace, wino_layout(g, Cin, Cout, WNY));
     // phase 1 (depth slab, halo exchange in flight): weight transform + the
     // interior z tiles' input transform (no halo plane in their windows);
     // phase 2: the first / last z tiles (halo planes now present), GEMM, output
@@ -4727,7 +4700,7 @@ static int fwd_wino(const float* x, int64_t B, int64_t H, int64_t W, int64_t D, 
         return check_launch("conv3d winograd fwd (x3, phase 1)");
     }
     WINO_INPUT(dim3(grid_for(g.T * Cin, 256)), s, x, phase == 2 ? ge : g, (int)Cin, ws.U);
-    wino_gemm_x3(ws, g.T, (int)Cin, (int)Cout, wino_points(), s, true);
+    launch_gemm_x3(ws.U, ws.V, ws.M, g.T, (int)Cin, (int)Cout, wino_points(), s, true);
     Epi o{};
     o.bias = bias; o.scale = bn_scale; o.shift = bn_shift; o.res = residual;
     o.res_mode = residual ? 1 : 0; o.relu = relu; o.z = z_out; o.y = y; o.ldy = Cout;
@@ -4756,14 +4729,93 @@ extern "C" int m3d_conv3d_fwd_wino_keep(const float* x, int64_t B, int64_t H, in
                     z_out, y, u_keep, workspace, ws_bytes, st(s));
 }
 
+// the data-gradient output transform: dx over the (halo-extended) grid, or,
+// for a depth slab with dx_halo, interior planes into dx (depth dl) and the
+// neighbours' planes into dx_halo [B][H][W][2][C]
+template <int NY>
+static void wino_dgrad_out(const float* Mt, const WinoGeom& g, int C, float* dx, int accumulate,
+                           float* dx_halo, int hlo, int dl, hipStream_t hs, const Epi* fb) {
+    Epi o{};
+    if (fb) o = *fb;                 // the fused BN backward's fields
+    o.y = dx; o.ldy = C; o.accumulate = accumulate;
+    const dim3 grid(grid_for(g.T * C, 256));
+    if (fb) {
+        hipLaunchKernelGGL((wino_output_bn_kernel<WNZ, NY>), grid, dim3(256), 0, hs, Mt, g, C, o);
+        return;
+    }
+    if (dx_halo) {
+        o.yh = dx_halo; o.hlo = hlo; o.dl = dl;
+        hipLaunchKernelGGL((wino_output_halo_kernel<WNZ, NY>), grid, dim3(256), 0, hs, Mt, g, C, o);
+        return;
+    }
+    hipLaunchKernelGGL((wino_output_kernel<WNZ, NY>), grid, dim3(256), 0, hs, Mt, g, C, o);
+}
+
+// the data gradient's launches on F(NY x 2 x 4) tiles (geometry g, workspace ws)
+template <int NY>
+static void bwd_data_wino_launch(const float* dz, const float* w, const WinoGeom& g, const WinoWs& ws, int Cin,
+                                 int Cout, float* dx, int32_t accumulate, float* dx_halo, int hlo, int dl,
+                                 bool v_ready, const Epi* fb, hipStream_t hs) {
+    const dim3 wgrid(grid_for((int64_t)Cin * Cout, 256)), igrid(grid_for(g.T * Cout, 256));
+    if (!v_ready)
+        hipLaunchKernelGGL((wino_weight_kernel<WNZ, true, NY>), wgrid, dim3(256), 0, hs, w, Cin, Cout, 1, ws.V);
+    hipLaunchKernelGGL((wino_input_kernel<WNZ, false, false, NY>), igrid, dim3(256), 0, hs, dz, g, Cout, ws.U);
+    launch_gemm_x3(ws.U, ws.V, ws.M, g.T, Cout, Cin, wino_points(NY), hs, true, g.gate);
+    wino_dgrad_out<NY>(ws.M, g, Cin, dx, accumulate, dx_halo, hlo, dl, hs, fb);
+}
+
 // dx [B,H,W,D,Cin] = conv_transpose(dz [B,H,W,OD,Cout]): a 'same'-type 3x3x3
 // correlation of dz with the flipped, transposed kernel, tiles over dx's grid,
 // dz read at z = 2tz - (2 - pz) + k.
 static int bwd_data_wino(const float* dz, const float* w, int64_t B, int64_t H, int64_t W, int64_t D,
                          int64_t Cin, int64_t Cout, int64_t OD, int32_t pz, float* dx, int32_t accumulate,
-                         void* workspace, size_t ws_bytes, hipStream_t s, float* dx_halo = nullptr,
-                         int hlo = 0, bool v_ready = false, const Epi* fb = nullptr, int ny = 0,
-                         const void* v_ext = nullptr, int rs_mode = 0);
+                         void* workspace, size_t ws_bytes, hipStream_t hs, float* dx_halo = nullptr,
+                         int hlo = 0, bool v_ready = false, const Epi* fb = nullptr, int ny_arg = 0,
+                         const void* v_ext = nullptr, int rs_mode = 0) {
+    int rc = wino_check(B, H, W, D, OD, pz, Cin, Cout);
+    if (rc) return rc;
+    if (wino_per_item(B, H, W, D, OD, Cin, Cout)) {
+        const int64_t dxd = dx_halo ? OD : D;          // dx depth: the slab's interior, or the full grid
+        for (int64_t b = 0; b < B; ++b) {
+            rc = bwd_data_wino(dz + b * H * W * OD * Cout, w, 1, H, W, D, Cin, Cout, OD, pz, dx + b * H * W * dxd * Cin,
+                               accumulate, workspace, ws_bytes, hs,
+                               dx_halo ? dx_halo + b * H * W * 2 * Cin : nullptr, hlo, v_ready || b > 0, nullptr,
+                               ny_arg, v_ext, RS_OFF);        // (the per-item loop stays dense)
+            if (rc) return rc;
+        }
+        return M3D_OK;
+    }
+    const int ny = ny_arg ? ny_arg : wino_dgrad_ny();
+    WinoGeom g = wino_geom(B, H, W, D, OD, 2 - pz, ny);
+    // the layout this call uses (its tile_y may differ from the library's default)
+    if (ws_bytes < wino_ws_need(g, Cout, Cin, ny))
+        return einval("conv3d winograd: workspace too small");
+    // the roles of Cin / Cout swapped (V'[P][Cout][Cin], U'[P][T][Cout])
+    const WinoLayout lay = wino_layout(g, Cout, Cin, ny);
+    WinoWs ws = wino_ws(workspace, lay);
+    if (v_ext) {                        // transformed by m3d_conv3d_wino_weight_v (dgrad 1, this tile_y)
+        ws.V = static_cast<float*>(const_cast<void*>(v_ext));
+        v_ready = true;
+    }
+    const int ci = (int)Cin, co = (int)Cout, dl = (int)OD;
+    // row-sparse dz (the RPN head's gradient): scan, gate the launches below on the
+    // outcome and enqueue the sparse launches behind their own gate
+    const int64_t rows = B * H * W * OD;
+    const int cap = rs_cap(rows);
+    const size_t um = lay.total - lay.u;            // the U and M regions
+    if (!dx_halo && !fb && rs_attempt(rs_mode, rows, Cin, Cout) && rs_dgrad_bytes(cap, Cin, Cout) <= um &&
+        (int64_t)cap * 27 * Cin * 4 < 0xFFFFFFF0LL && 27 * Cin * Cout * 2 < 0xFFFFFFF0LL) {
+        const RsHdr hd = rs_hdr(static_cast<char*>(workspace) + lay.total, rows);
+        g.gate = hd.h + RS_SKIP_DENSE;
+        rs_dgrad_launch(dz, w, B, (int)H, (int)W, (int)D, (int)OD, pz, ci, co, dx, accumulate,
+                        reinterpret_cast<char*>(ws.U), cap, hd, hs);
+    }
+    if (ny == 4)
+        bwd_data_wino_launch<4>(dz, w, g, ws, ci, co, dx, accumulate, dx_halo, hlo, dl, v_ready, fb, hs);
+    else
+        bwd_data_wino_launch<2>(dz, w, g, ws, ci, co, dx, accumulate, dx_halo, hlo, dl, v_ready, fb, hs);
+    return check_launch("conv3d winograd bwd-data");
+}
 
 // The same two entry points for convs that share one kernel across calls (the
 // RPN head's rpn_conv_shared1 on P2..P6, core/models.py:512-557): with
@@ -4919,386 +4971,9 @@ extern "C" int m3d_conv3d_bwd_data_wino_xv(const float* dz, const float* w, int6
                          false, nullptr, ny, v);
 }
 
-// ---- row-sparse output gradients --------------------------------------------
-// The RPN loss leaves a gradient only on the sampled anchors, so the dz that
-// reaches rpn_conv_shared1 has a few hundred non-zero voxel rows out of 10^5.
-// bwd_data_wino / bwd_weight_wino scan dz on the device (a probe of evenly
-// spaced rows first: a dense dz costs no pass over the tensor), and either run
-// the Winograd launches (state DENSE) or a gather -> split GEMM -> scatter
-// over the active rows only (state SPARSE).  Both sets of launches are always
-// enqueued -- the step is replayed from a graph -- and every workgroup of the
-// set that is not due returns on a gate word of the header below.
-// Header (ints) behind the call's [WT][V][U][M] layout:
-//   h[RS_STATE] 0 undecided (after the probe) / RS_DENSE / RS_SPARSE
-//   h[RS_SKIP_DENSE] != 0: the dense kernels return; h[RS_SKIP_SPARSE] != 0: the sparse ones
-//   h[RS_N] active rows (SPARSE);  h[RS_PROBE] != 0: the probe found dz dense (written by the probe
-//   alone: the scan kernels read it, and never a word that one of them writes);
-//   idx[RS_CAP_MAX] the active rows, ascending;
-//   blk[rows / 64] active rows per 64-row group;  slot[rows] row -> compact slot or -1
-constexpr int RS_CAP_MAX = 4096;        // most active rows the sparse path takes ...
-constexpr int RS_CAP_DIV = 32;          // ... and at most rows / 32
-constexpr int RS_PROBE_ROWS = 256;      // rows the probe reads
-constexpr int RS_PROBE_DIV = 8;         // probe: DENSE when more than 1 / 8 of them are active
-constexpr int RS_BLK = 64;              // rows per scan block
-// RS_AUTO attempts the sparse path when the layer's direct-equivalent work 2 * 27 * rows * Cin * Cout reaches
-// this.  A dense call pays 18-30 us for the attempt (probe, two scan launches that return, the gated sparse
-// launches; DESIGN.md 5, scripts/rowsparse_overhead.py), which is to stay near 2 % of the call: 0.9 TFLOP
-// admits rpn_conv_shared1 on P2 at 128^3 (0.93 TFLOP: 0.9-1.7 % / 1.6-2.4 % of its dense data / weight
-// gradient) and leaves out fpn_p2 (0.46 TFLOP: 2.9 % / 3.2 %) and P3 (0.23 TFLOP).  The benchmark's P2
-// sits 3 % above the threshold: a smaller volume runs dense (DESIGN.md 5 says what would lift that)
-constexpr double RS_MIN_FLOP = 9e11;
-enum { RS_STATE = 0, RS_SKIP_DENSE = 1, RS_SKIP_SPARSE = 2, RS_N = 3, RS_PROBE = 4, RS_HDR_INTS = 64 };
-enum { RS_UNDECIDED = 0, RS_DENSE = 1, RS_SPARSE = 2 };
-
-// rs_mode, a per-call argument of m3d_conv3d_bwd_data_wino_rs / m3d_conv3d_bwd_weight_wino_ux (a test
-// and A/B hook; the library holds no mode, every other entry point runs RS_AUTO): RS_AUTO attempts from
-// RS_MIN_FLOP on, RS_OFF runs exactly the dense launches, ungated, RS_ALWAYS attempts at every size.
-enum { RS_AUTO = 0, RS_OFF = 1, RS_ALWAYS = 2 };
-
-static size_t rs_al(size_t b) { return (b + 255) & ~(size_t)255; }
-static size_t rs_hdr_bytes(int64_t rows) {
-    return rs_al(sizeof(int) * (RS_HDR_INTS + RS_CAP_MAX)) + rs_al(sizeof(int) * (size_t)((rows + RS_BLK - 1) / RS_BLK)) +
-           rs_al(sizeof(int) * (size_t)rows);
-}
-struct RsHdr { int *h, *idx, *blk, *slot; };
-static RsHdr rs_hdr(void* base, int64_t rows) {
-    RsHdr r{};
-    char* p = static_cast<char*>(base);
-    r.h = reinterpret_cast<int*>(p);
-    r.idx = r.h + RS_HDR_INTS;
-    p += rs_al(sizeof(int) * (RS_HDR_INTS + RS_CAP_MAX));
-    r.blk = reinterpret_cast<int*>(p);
-    p += rs_al(sizeof(int) * (size_t)((rows + RS_BLK - 1) / RS_BLK));
-    r.slot = reinterpret_cast<int*>(p);
-    return r;
-}
-static int rs_cap(int64_t rows) {
-    const int64_t c = rows / RS_CAP_DIV;
-    return (int)(c > RS_CAP_MAX ? RS_CAP_MAX : c);
-}
-// whether this call scans dz at all (host side: shapes and the process mode only)
-static bool rs_attempt(int mode, int64_t rows, int64_t Cin, int64_t Cout) {
-    if (mode == RS_OFF) return false;
-    if (rs_cap(rows) < 1 || rows > 0x7FFFFFFF) return false;
-    return mode == RS_ALWAYS || 2.0 * 27.0 * (double)rows * (double)Cin * (double)Cout >= RS_MIN_FLOP;
-}
-
-// this lane's part of "row has an element != 0" (-0.0f is not, a NaN is), C % 4 == 0
-__device__ __forceinline__ bool rs_lane_active(const float* __restrict__ row, int C, int lane) {
-    bool a = false;
-    for (int c = lane * 4; c < C; c += 256) {
-        const float4 v = *reinterpret_cast<const float4*>(row + c);
-        a |= (v.x != 0.0f) | (v.y != 0.0f) | (v.z != 0.0f) | (v.w != 0.0f);
-    }
-    return a;
-}
-
-// one workgroup of 16 waves: RS_PROBE_ROWS evenly spaced rows, 16 per wave
-__global__ __launch_bounds__(1024) void rs_probe_kernel(const float* __restrict__ dz, int64_t rows, int C,
-                                                        int* __restrict__ h) {
-    __shared__ int cnt[16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int ns = rows < RS_PROBE_ROWS ? (int)rows : RS_PROBE_ROWS;
-    unsigned m = 0;
-#pragma unroll
-    for (int k = 0; k < RS_PROBE_ROWS / 16; ++k) {
-        const int i = wave * (RS_PROBE_ROWS / 16) + k;
-        bool a = false;
-        // evenly spaced, each sample 37 rows further along than the last: a plain stride is a multiple of
-        // the depth at the step's shapes and would read one z plane and one x phase only
-        if (i < ns) a = rs_lane_active(dz + (((int64_t)i * rows / ns + (int64_t)i * 37) % rows) * C, C, lane);
-        m |= (a ? 1u : 0u) << k;
-    }
-    int c = 0;
-#pragma unroll
-    for (int k = 0; k < RS_PROBE_ROWS / 16; ++k) c += __ballot((m >> k) & 1u) != 0ull ? 1 : 0;
-    if (lane == 0) cnt[wave] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int a = 0;
-        for (int w = 0; w < 16; ++w) a += cnt[w];
-        const bool dense = a * RS_PROBE_DIV > ns;
-        h[RS_PROBE] = dense ? 1 : 0;
-        h[RS_STATE] = dense ? RS_DENSE : RS_UNDECIDED;
-        h[RS_SKIP_DENSE] = 0;
-        h[RS_SKIP_SPARSE] = 1;
-        h[RS_N] = 0;
-    }
-}
-
-// slot[row] = row active (0 / 1), blk[block] = active rows of the block's RS_BLK rows
-__global__ __launch_bounds__(256) void rs_flag_kernel(const float* __restrict__ dz, int64_t rows, int C,
-                                                      const int* __restrict__ h, int* __restrict__ blk,
-                                                      int* __restrict__ slot) {
-    if (h[RS_PROBE]) return;
-    __shared__ int cnt[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t r0 = (int64_t)blockIdx.x * RS_BLK + wave * 16;
-    unsigned m = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        bool a = false;
-        if (r0 + k < rows) a = rs_lane_active(dz + (r0 + k) * C, C, lane);
-        m |= (a ? 1u : 0u) << k;
-    }
-    int c = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const int act = __ballot((m >> k) & 1u) != 0ull ? 1 : 0;
-        if (lane == 0 && r0 + k < rows) slot[r0 + k] = act;
-        c += act;
-    }
-    if (lane == 0) cnt[wave] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) blk[blockIdx.x] = cnt[0] + cnt[1] + cnt[2] + cnt[3];
-}
-
-// Everything between the scan's flags and the sparse GEMM, in one launch (each launch a dense call
-// makes for nothing costs it about 3.5 us).  Every workgroup sums blk itself -- the count n, hence the
-// state, and the count before its own rows -- so no launch stands between the flags and their prefix.
-// Block ranges: [0, nb_idx) 256 rows each: slot[row] = compact slot or -1, idx[slot] = row (ascending:
-// slots follow the row order), and the active rows gathered, dzc[slot] = dz[row] and, for the weight
-// gradient, xg[tap][slot] = x at the tap's input voxel ('same' padding: zero outside);
-// then nb_zero blocks zero rows n..cap of dzc / xg; then (data gradient) the three bf16 planes of w.
-struct RsPack {
-    const float* dz = nullptr;
-    int64_t rows = 0;
-    int C = 0, cap = 0;
-    int* h = nullptr;
-    const int* blk = nullptr;
-    int* slot = nullptr;
-    int* idx = nullptr;
-    float* dzc = nullptr;                  // [cap][C]
-    const float* x = nullptr;              // weight gradient: x [B][H][W][D][Cx] -> xg [27][cap][Cx]
-    float* xg = nullptr;
-    int H = 0, W = 0, D = 0, OD = 0, pz = 0, Cx = 0;
-    const float* w = nullptr;              // data gradient: w (nw elements) -> planes wp [3][nw]
-    unsigned short* wp = nullptr;
-    int64_t nw = 0;
-    unsigned nb_idx = 0, nb_zero = 0;
-};
-constexpr int RS_SPLIT_PER = 2048;         // elements of w per split block
-
-__device__ __forceinline__ void rs_copy_row(const float* __restrict__ s, float* __restrict__ d, int C, int lane,
-                                            bool on) {
-    for (int c = lane * 4; c < C; c += 256) {
-        float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (on) v = *reinterpret_cast<const float4*>(s + c);
-        *reinterpret_cast<float4*>(d + c) = v;
-    }
-}
-
-__global__ __launch_bounds__(256) void rs_pack_kernel(RsPack p) {
-    // the probe's verdict, in a word no launch of this kernel writes: the exit is the same for every wave
-    // of every workgroup (block 0 publishes the final state below, in words this kernel never reads)
-    if (p.h[RS_PROBE]) return;
-    __shared__ int red[2][4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t nblk = (p.rows + RS_BLK - 1) / RS_BLK;
-    const bool ib = blockIdx.x < p.nb_idx;
-    const int64_t g0 = ib ? (int64_t)blockIdx.x * 4 : 0;        // this block's first 64-row group
-    int tot = 0, pre = 0;
-    for (int64_t i = tid; i < nblk; i += 256) {
-        const int c = p.blk[i];
-        tot += c;
-        if (i < g0) pre += c;
-    }
-#pragma unroll
-    for (int o = 32; o; o >>= 1) {
-        tot += __shfl_xor(tot, o);
-        pre += __shfl_xor(pre, o);
-    }
-    if (lane == 0) { red[0][wave] = tot; red[1][wave] = pre; }
-    __syncthreads();
-    const int n = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-    const bool sparse = n <= p.cap;
-    if (blockIdx.x == 0 && tid == 0) {
-        p.h[RS_STATE] = sparse ? RS_SPARSE : RS_DENSE;
-        p.h[RS_SKIP_DENSE] = sparse ? 1 : 0;
-        p.h[RS_SKIP_SPARSE] = sparse ? 0 : 1;
-        p.h[RS_N] = sparse ? n : 0;
-    }
-    if (!sparse) return;
-    if (ib) {
-        const int64_t g = g0 + wave;
-        if (g >= nblk) return;
-        int base = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-        for (int q = 0; q < wave; ++q) base += p.blk[g0 + q];
-        const int64_t r = g * RS_BLK + lane;
-        const bool act = r < p.rows && p.slot[r] != 0;
-        unsigned long long m = __ballot(act);
-        const int s = base + __popcll(m & ((1ull << lane) - 1ull));
-        if (r < p.rows) p.slot[r] = act ? s : -1;
-        if (act) p.idx[s] = (int)r;                    // s < n <= cap <= RS_CAP_MAX
-        for (int k = 0; m; ++k) {                      // the group's active rows, one after the other
-            const int j = __ffsll(m) - 1;
-            m &= m - 1;
-            const int64_t row = g * RS_BLK + j;
-            const int sk = base + k;
-            if (!p.dzc) break;                         // (the scan alone)
-            rs_copy_row(p.dz + row * p.C, p.dzc + (int64_t)sk * p.C, p.C, lane, true);
-            if (!p.xg) continue;
-            int64_t t = row;
-            const int zo = (int)(t % p.OD); t /= p.OD;
-            const int xo = (int)(t % p.W); t /= p.W;
-            const int yo = (int)(t % p.H);
-            const int64_t b = t / p.H;
-            // all 27 taps' loads of a 256-channel chunk in flight before the stores (one wave per row:
-            // tap after tap the copies ran at one load latency each, 54 us of the 128^3 P2 call)
-            for (int c = lane * 4; c < p.Cx; c += 256) {
-                float4 v[27];
-#pragma unroll
-                for (int tap = 0; tap < 27; ++tap) {
-                    const int yi = yo + tap / 9 - 1, xi = xo + (tap / 3) % 3 - 1, zi = zo + tap % 3 - p.pz;
-                    const bool in = (unsigned)yi < (unsigned)p.H && (unsigned)xi < (unsigned)p.W &&
-                                    (unsigned)zi < (unsigned)p.D;
-                    v[tap] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                    if (in)
-                        v[tap] = *reinterpret_cast<const float4*>(
-                            p.x + (((b * p.H + yi) * p.W + xi) * p.D + zi) * p.Cx + c);
-                }
-#pragma unroll
-                for (int tap = 0; tap < 27; ++tap)
-                    *reinterpret_cast<float4*>(p.xg + ((int64_t)tap * p.cap + sk) * p.Cx + c) = v[tap];
-            }
-        }
-        return;
-    }
-    const unsigned bz = blockIdx.x - p.nb_idx;
-    if (bz < p.nb_zero) {
-        const int r = (int)bz * 4 + wave;
-        if (r < n || r >= p.cap) return;
-        rs_copy_row(p.dz, p.dzc + (int64_t)r * p.C, p.C, lane, false);
-        if (p.xg)
-            for (int tap = 0; tap < 27; ++tap)
-                rs_copy_row(p.x, p.xg + ((int64_t)tap * p.cap + r) * p.Cx, p.Cx, lane, false);
-        return;
-    }
-    const int64_t i0 = (int64_t)(bz - p.nb_zero) * RS_SPLIT_PER + tid;
-#pragma unroll
-    for (int k = 0; k < RS_SPLIT_PER / 256; ++k) {
-        const int64_t i = i0 + k * 256;
-        if (i >= p.nw) break;
-        uint32_t hi, mi, lo;
-        split3(p.w[i], hi, mi, lo);
-        p.wp[i] = (unsigned short)hi;
-        p.wp[p.nw + i] = (unsigned short)mi;
-        p.wp[2 * p.nw + i] = (unsigned short)lo;
-    }
-}
-
-// probe, flags, pack: q holds the pack's operands (x / xg or w / wp, dzc); the rest is filled in here
-static void rs_scan(const float* dz, int64_t rows, int C, int cap, const RsHdr& hd, RsPack q, hipStream_t s) {
-    const int64_t nblk = (rows + RS_BLK - 1) / RS_BLK;
-    q.dz = dz; q.rows = rows; q.C = C; q.cap = cap;
-    q.h = hd.h; q.blk = hd.blk; q.slot = hd.slot; q.idx = hd.idx;
-    q.nb_idx = (unsigned)((nblk + 3) / 4);
-    q.nb_zero = q.dzc ? (unsigned)((cap + 3) / 4) : 0;
-    const unsigned nb_split = (unsigned)((q.nw + RS_SPLIT_PER - 1) / RS_SPLIT_PER);
-    hipLaunchKernelGGL(rs_probe_kernel, dim3(1), dim3(1024), 0, s, dz, rows, C, hd.h);
-    hipLaunchKernelGGL(rs_flag_kernel, dim3((unsigned)nblk), dim3(256), 0, s, dz, rows, C, hd.h, hd.blk, hd.slot);
-    hipLaunchKernelGGL(rs_pack_kernel, dim3(q.nb_idx + q.nb_zero + nb_split), dim3(256), 0, s, q);
-}
-
-// The scan alone (tests): ws receives the header of the layout above for `rows` rows.
-extern "C" size_t m3d_conv3d_rowsparse_scan_bytes(int64_t rows) { return rows > 0 ? rs_hdr_bytes(rows) : 0; }
-extern "C" int m3d_conv3d_rowsparse_scan(const float* dz, int64_t rows, int64_t C, int32_t cap, void* ws,
-                                         size_t ws_bytes, m3d_stream_t s) {
-    if (rows <= 0 || rows > 0x7FFFFFFF || C <= 0 || C % 4) return einval("rowsparse_scan: rows > 0 and C a positive multiple of 4");
-    if (cap < 0 || cap > RS_CAP_MAX) return einval("rowsparse_scan: cap must be in [0, 4096]");
-    if (!dz || !ws || ws_bytes < rs_hdr_bytes(rows)) return einval("rowsparse_scan: workspace missing or too small");
-    rs_scan(dz, rows, (int)C, cap, rs_hdr(ws, rows), RsPack{}, st(s));
-    return check_launch("rowsparse_scan");
-}
-
-// dx[v][:] (+)= sum over the 27 taps, in tap order, of ct[slot(dz row of the tap)][tap][:]
-// where that row is inside dz and active: dx voxel (y, x, z) takes tap (ky, kx, kz)
-// from dz (y - ky + 1, x - kx + 1, z - kz + pz).  A workgroup owns 8 consecutive
-// voxels; a voxel without an active neighbour is zero-filled (left as it is
-// under accumulate).
-constexpr int RS_VOX = 8;
-__global__ __launch_bounds__(256) void rs_dgrad_out_kernel(const float* __restrict__ ct, int64_t nvox, int H, int W,
-                                                           int D, int OD, int pz, int C, int accumulate,
-                                                           const int* __restrict__ h,
-                                                           const int* __restrict__ slot, float* __restrict__ dx) {
-    if (h[RS_SKIP_SPARSE]) return;
-    __shared__ int ss[RS_VOX * 27];
-    __shared__ int hit[RS_VOX];
-    const int tid = threadIdx.x;
-    const int64_t v0 = (int64_t)blockIdx.x * RS_VOX;
-    if (tid < RS_VOX) hit[tid] = 0;
-    __syncthreads();
-    if (tid < RS_VOX * 27) {
-        const int j = tid / 27, tap = tid % 27, ky = tap / 9, kx = (tap / 3) % 3, kz = tap % 3;
-        int sl = -1;
-        int64_t t = v0 + j;
-        if (t < nvox) {
-            const int z = (int)(t % D); t /= D;
-            const int xx = (int)(t % W); t /= W;
-            const int y = (int)(t % H);
-            const int64_t b = t / H;
-            const int yo = y - ky + 1, xo = xx - kx + 1, zo = z - kz + pz;
-            if ((unsigned)yo < (unsigned)H && (unsigned)xo < (unsigned)W && (unsigned)zo < (unsigned)OD)
-                sl = slot[((b * H + yo) * W + xo) * OD + zo];
-        }
-        ss[tid] = sl;
-        if (sl >= 0) hit[j] = 1;
-    }
-    __syncthreads();
-    const int L = C / 4;
-    for (int q = tid; q < RS_VOX * L; q += 256) {
-        const int j = q / L, c = (q % L) * 4;
-        if (v0 + j >= nvox) break;
-        float* o = dx + (v0 + j) * C + c;
-        if (!hit[j]) {
-            if (!accumulate) *reinterpret_cast<float4*>(o) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            continue;
-        }
-        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (accumulate) a = *reinterpret_cast<const float4*>(o);
-        for (int tap = 0; tap < 27; ++tap) {
-            const int sl = ss[j * 27 + tap];
-            if (sl < 0) continue;
-            const float4 v = *reinterpret_cast<const float4*>(ct + ((int64_t)sl * 27 + tap) * C + c);
-            a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-        }
-        *reinterpret_cast<float4*>(o) = a;
-    }
-}
-
-// bytes the sparse paths lay out from the U region on (both regions belong to
-// the path that runs): data gradient dzc [cap][Cout], w planes, ct [cap][27][Cin];
-// weight gradient dzc [cap][Cout], xg [27][cap][Cin]
-static size_t rs_dgrad_bytes(int cap, int64_t Cin, int64_t Cout) {
-    return rs_al(4 * (size_t)cap * Cout) + rs_al(6 * 27 * (size_t)Cin * Cout) + rs_al(4 * (size_t)cap * 27 * Cin);
-}
-static size_t rs_wgrad_bytes(int cap, int64_t Cin, int64_t Cout) {
-    return rs_al(4 * (size_t)cap * Cout) + rs_al(4 * 27 * (size_t)cap * Cin);
-}
-
-// the scan and the sparse data gradient's launches (gated on h[RS_SKIP_SPARSE]); um: the U region
-static void rs_dgrad_launch(const float* dz, const float* w, int64_t B, int H, int W, int D, int OD, int pz, int Cin,
-                            int Cout, float* dx, int accumulate, char* um, int cap, const RsHdr& hd, hipStream_t s) {
-    float* dzc = reinterpret_cast<float*>(um);
-    unsigned short* wp = reinterpret_cast<unsigned short*>(um + rs_al(4 * (size_t)cap * Cout));
-    float* ct = reinterpret_cast<float*>(um + rs_al(4 * (size_t)cap * Cout) + rs_al(6 * 27 * (size_t)Cin * Cout));
-    RsPack q{};
-    q.dzc = dzc; q.w = w; q.wp = wp; q.nw = (int64_t)27 * Cin * Cout;
-    rs_scan(dz, B * H * W * OD, Cout, cap, hd, q, s);
-    // ct[r][tap * Cin + c] = sum_n dzc[r][n] w[tap][c][n]: A = dzc (fp32), B = w as [27 Cin][Cout] planes
-    WinoWs g{};
-    g.U = dzc;
-    g.V = reinterpret_cast<float*>(wp);
-    g.M = ct;
-    wino_gemm_x3(g, cap, Cout, 27 * Cin, 1, s, true, hd.h + RS_SKIP_SPARSE, hd.h + RS_N);
-    const int64_t nvox = B * H * W * D;
-    hipLaunchKernelGGL(rs_dgrad_out_kernel, dim3((unsigned)((nvox + RS_VOX - 1) / RS_VOX)), dim3(256), 0, s, ct, nvox,
-                       H, W, D, OD, pz, Cin, accumulate, hd.h, hd.slot, dx);
-}
-
 // The unfused data gradient with every per-call choice as an argument: v_ready and tile_y as
 // m3d_conv3d_bwd_data_wino_vy, v (NULL, or the transformed weights of m3d_conv3d_wino_weight_v at this
-// tile_y, as m3d_conv3d_bwd_data_wino_xv) and rs_mode (RS_AUTO / RS_OFF / RS_ALWAYS above).
+// tile_y, as m3d_conv3d_bwd_data_wino_xv) and rs_mode (RS_AUTO / RS_OFF / RS_ALWAYS, conv_types.h).
 extern "C" int m3d_conv3d_bwd_data_wino_rs(const float* dz, const float* w, int64_t B, int64_t H, int64_t W,
                                            int64_t D, int64_t Cin, int64_t Cout, int64_t OD, int32_t pz, float* dx,
                                            int32_t accumulate, void* workspace, size_t ws_bytes, int32_t v_ready,
@@ -5308,91 +4983,6 @@ extern "C" int m3d_conv3d_bwd_data_wino_rs(const float* dz, const float* w, int6
     if (rs_mode < RS_AUTO || rs_mode > RS_ALWAYS) return einval("conv3d winograd bwd-data: rs_mode must be 0, 1 or 2");
     return bwd_data_wino(dz, w, B, H, W, D, Cin, Cout, OD, pz, dx, accumulate, workspace, ws_bytes, st(s), nullptr, 0,
                          v_ready != 0, nullptr, ny, v, rs_mode);
-}
-
-// the data-gradient output transform: dx over the (halo-extended) grid, or,
-// for a depth slab with dx_halo, interior planes into dx (depth dl) and the
-// neighbours' planes into dx_halo [B][H][W][2][C]
-template <int NY>
-static void wino_dgrad_out(const float* Mt, const WinoGeom& g, int C, float* dx, int accumulate,
-                           float* dx_halo, int hlo, int dl, hipStream_t hs, const Epi* fb) {
-    Epi o{};
-    if (fb) o = *fb;                 // the fused BN backward's fields
-    o.y = dx; o.ldy = C; o.accumulate = accumulate;
-    const dim3 grid(grid_for(g.T * C, 256));
-    if (fb) {
-        hipLaunchKernelGGL((wino_output_bn_kernel<WNZ, NY>), grid, dim3(256), 0, hs, Mt, g, C, o);
-        return;
-    }
-    if (dx_halo) {
-        o.yh = dx_halo; o.hlo = hlo; o.dl = dl;
-        hipLaunchKernelGGL((wino_output_halo_kernel<WNZ, NY>), grid, dim3(256), 0, hs, Mt, g, C, o);
-        return;
-    }
-    hipLaunchKernelGGL((wino_output_kernel<WNZ, NY>), grid, dim3(256), 0, hs, Mt, g, C, o);
-}
-
-// the data gradient's launches on F(NY x 2 x 4) tiles (geometry g, workspace ws)
-template <int NY>
-static void bwd_data_wino_launch(const float* dz, const float* w, const WinoGeom& g, const WinoWs& ws, int Cin,
-                                 int Cout, float* dx, int32_t accumulate, float* dx_halo, int hlo, int dl,
-                                 bool v_ready, const Epi* fb, hipStream_t hs) {
-    const dim3 wgrid(grid_for((int64_t)Cin * Cout, 256)), igrid(grid_for(g.T * Cout, 256));
-    if (!v_ready)
-        hipLaunchKernelGGL((wino_weight_kernel<WNZ, true, NY>), wgrid, dim3(256), 0, hs, w, Cin, Cout, 1, ws.V);
-    hipLaunchKernelGGL((wino_input_kernel<WNZ, false, false, NY>), igrid, dim3(256), 0, hs, dz, g, Cout, ws.U);
-    wino_gemm_x3(ws, g.T, Cout, Cin, wino_points(NY), hs, true, g.gate);
-    wino_dgrad_out<NY>(ws.M, g, Cin, dx, accumulate, dx_halo, hlo, dl, hs, fb);
-}
-
-static int bwd_data_wino(const float* dz, const float* w, int64_t B, int64_t H, int64_t W, int64_t D,
-                         int64_t Cin, int64_t Cout, int64_t OD, int32_t pz, float* dx, int32_t accumulate,
-                         void* workspace, size_t ws_bytes, hipStream_t hs, float* dx_halo, int hlo, bool v_ready,
-                         const Epi* fb, int ny_arg, const void* v_ext, int rs_mode) {
-    int rc = wino_check(B, H, W, D, OD, pz, Cin, Cout);
-    if (rc) return rc;
-    if (wino_per_item(B, H, W, D, OD, Cin, Cout)) {
-        const int64_t dxd = dx_halo ? OD : D;          // dx depth: the slab's interior, or the full grid
-        for (int64_t b = 0; b < B; ++b) {
-            rc = bwd_data_wino(dz + b * H * W * OD * Cout, w, 1, H, W, D, Cin, Cout, OD, pz, dx + b * H * W * dxd * Cin,
-                               accumulate, workspace, ws_bytes, hs,
-                               dx_halo ? dx_halo + b * H * W * 2 * Cin : nullptr, hlo, v_ready || b > 0, nullptr,
-                               ny_arg, v_ext, RS_OFF);        // (the per-item loop stays dense)
-            if (rc) return rc;
-        }
-        return M3D_OK;
-    }
-    const int ny = ny_arg ? ny_arg : wino_dgrad_ny();
-    WinoGeom g = wino_geom(B, H, W, D, OD, 2 - pz, ny);
-    // the layout this call uses (its tile_y may differ from the library's default)
-    if (ws_bytes < wino_ws_need(g, Cout, Cin, ny))
-        return einval("conv3d winograd: workspace too small");
-    // same layout with the roles of Cin/Cout swapped (V'[P][Cout][Cin], U'[P][T][Cout])
-    WinoWs ws = wino_ws(workspace, g, Cout, Cin, ny);
-    float* const ws_u = ws.U;
-    if (v_ext) {                        // transformed by m3d_conv3d_wino_weight_v (dgrad 1, this tile_y)
-        ws.V = static_cast<float*>(const_cast<void*>(v_ext));
-        v_ready = true;
-    }
-    const int ci = (int)Cin, co = (int)Cout, dl = (int)OD;
-    // row-sparse dz (the RPN head's gradient): scan, gate the launches below on the
-    // outcome and enqueue the sparse launches behind their own gate
-    const int64_t rows = B * H * W * OD;
-    const int cap = rs_cap(rows);
-    const size_t lay = wino_ws_layout(g, Cout, Cin, ny);
-    const size_t um = lay - (size_t)(reinterpret_cast<char*>(ws_u) - static_cast<char*>(workspace));
-    if (!dx_halo && !fb && rs_attempt(rs_mode, rows, Cin, Cout) && rs_dgrad_bytes(cap, Cin, Cout) <= um &&
-        (int64_t)cap * 27 * Cin * 4 < 0xFFFFFFF0LL && 27 * Cin * Cout * 2 < 0xFFFFFFF0LL) {
-        const RsHdr hd = rs_hdr(static_cast<char*>(workspace) + lay, rows);
-        g.gate = hd.h + RS_SKIP_DENSE;
-        rs_dgrad_launch(dz, w, B, (int)H, (int)W, (int)D, (int)OD, pz, ci, co, dx, accumulate,
-                        reinterpret_cast<char*>(ws_u), cap, hd, hs);
-    }
-    if (ny == 4)
-        bwd_data_wino_launch<4>(dz, w, g, ws, ci, co, dx, accumulate, dx_halo, hlo, dl, v_ready, fb, hs);
-    else
-        bwd_data_wino_launch<2>(dz, w, g, ws, ci, co, dx, accumulate, dx_halo, hlo, dl, v_ready, fb, hs);
-    return check_launch("conv3d winograd bwd-data");
 }
 
 static int bwd_weight_wino(const float* x, const float* u_in, const float* dz, int64_t B,
@@ -5415,17 +5005,17 @@ static int bwd_weight_wino(const float* x, const float* u_in, const float* dz, i
     }
     WinoGeom g = wino_geom(B, H, W, OD, D, pz);
     g.halo = halo; g.hlo = hlo; g.hhi = hhi;
-    WinoWs ws = wino_ws(workspace, g, Cin, Cout);   // V <- dW_hat, U <- B^T x, M <- A dz
+    const WinoLayout lay = wino_layout(g, Cin, Cout, WNY);
+    WinoWs ws = wino_ws(workspace, lay);            // V <- dW_hat, U <- B^T x, M <- A dz
     // row-sparse dz (see rs_scan): the launches below return when the scan finds dz
     // sparse, and dw += xg[tap]^T dzc over the gathered active rows runs in their place
     const int* gate = nullptr;
     const int64_t rows = B * H * W * OD;
     const int cap = rs_cap(rows);
-    const size_t lay = wino_ws_layout(g, Cin, Cout, WNY);
-    const size_t um = lay - (size_t)(reinterpret_cast<char*>(ws.U) - static_cast<char*>(workspace));
+    const size_t um = lay.total - lay.u;            // the U and M regions
     if (x && !halo && (Cout > 64 || Cin <= 64) && rs_attempt(rs_mode, rows, Cin, Cout) &&
         rs_wgrad_bytes(cap, Cin, Cout) <= um) {
-        const RsHdr hd = rs_hdr(static_cast<char*>(workspace) + lay, rows);
+        const RsHdr hd = rs_hdr(static_cast<char*>(workspace) + lay.total, rows);
         gate = g.gate = hd.h + RS_SKIP_DENSE;
         float* dzc = ws.U;
         float* xg = reinterpret_cast<float*>(reinterpret_cast<char*>(ws.U) + rs_al(4 * (size_t)cap * Cout));
@@ -5556,10 +5146,10 @@ extern "C" size_t m3d_conv3d_rowsparse_header_offset(int64_t B, int64_t H, int64
                                                      int32_t pz, int64_t Cin, int64_t Cout, int32_t pass,
                                                      int32_t tile_y) {
     if (wino_check(B, H, W, D, OD, pz, Cin, Cout) || wino_per_item(B, H, W, D, OD, Cin, Cout)) return (size_t)-1;
-    if (pass == 1) return wino_ws_layout(wino_geom(B, H, W, OD, D, pz), Cin, Cout, WNY);
+    if (pass == 1) return wino_layout(wino_geom(B, H, W, OD, D, pz), Cin, Cout, WNY).total;
     if (pass != 0 || (tile_y != 0 && tile_y != 2 && tile_y != 4)) return (size_t)-1;
     const int ny = tile_y ? tile_y : wino_dgrad_ny();
-    return wino_ws_layout(wino_geom(B, H, W, D, OD, 2 - pz, ny), Cout, Cin, ny);
+    return wino_layout(wino_geom(B, H, W, D, OD, 2 - pz, ny), Cout, Cin, ny).total;
 }
 
 // The kept-U form that also receives x [B,H,W,D,Cin]: the dense launches read u as
@@ -5574,433 +5164,4 @@ extern "C" int m3d_conv3d_bwd_weight_wino_ux(const float* u, const float* x, con
     if (rs_mode < RS_AUTO || rs_mode > RS_ALWAYS) return einval("conv3d winograd bwd-weight: rs_mode must be 0, 1 or 2");
     return bwd_weight_wino(x, u, dz, B, H, W, D, Cin, Cout, OD, pz, dw, workspace, ws_bytes, s, nullptr, 0, 0,
                            rs_mode);
-}
-
-// ---- the RPN head's backward on the sampled anchors' rows ---------------------
-// Everything above rpn_conv_shared1 is 1x1x1, so the head's output gradient is
-// row-sparse from the loss down to the 3x3x3 conv: the active voxel rows are
-// found once, from the loss gradient itself (dlogits [R][2 apl], dbbox
-// [R][6 apl], R the level-concatenated rows, B = 1), and the whole chain
-//   rpn_class_raw + rpn_bbox_pred -> ReLU -> rpn_conv_shared2 -> ReLU -> rpn_conv_shared1
-// runs on compact [cap][C] matrices (rows n..cap zero).  rpn_conv_shared1 takes
-// the compact gradient and the row list directly, all levels in one set of
-// launches: the tap gather of rs_pack_kernel and one 27-batch split GEMM for
-// dw, one GEMM ct = dz1c w and rs_dgrad_out_kernel per level for dx (slots are
-// global over the levels).  Launch shapes are fixed by (R, cap): a graph replay
-// follows the data.  More than cap active rows is an error of the caller's
-// bound, made loud: the sticky word h[HC_OVERFLOW] counts it and dz3c is filled
-// with NaN, which every gradient of the step inherits.
-// Workspace: the header of rs_hdr (h[RS_SKIP_SPARSE] = 0, h[RS_N] = min(n, cap);
-// beside it h[HC_NRAW] = n, h[HC_OVERFLOW], h[HC_LEVEL0 + l] = first slot of
-// level l, l = 0..nlevels), then dz3c [cap][npad], s2c [cap][C2], s1c [cap][C1],
-// dz2c [cap][C2], dz1c [cap][C1], the planes of w1, ct [cap][27 C0], xg [27][cap][C0]
-// and the dw24 / dw2 chunk partials (double [cap / 64][C2][max(npad, C1)]).
-enum { HC_NRAW = 8, HC_OVERFLOW = 16, HC_LEVEL0 = 32 };
-constexpr int HC_CHUNK = 64;               // compact rows per dw24 / dw2 partial
-
-struct HcLevels {
-    const float* p[M3D_RPN_HEAD_MAX_LEVELS];
-    const float* s1[M3D_RPN_HEAD_MAX_LEVELS];
-    const float* s2[M3D_RPN_HEAD_MAX_LEVELS];
-    int row0[M3D_RPN_HEAD_MAX_LEVELS + 1];     // first row of each level; [n] = R
-    int H[M3D_RPN_HEAD_MAX_LEVELS], W[M3D_RPN_HEAD_MAX_LEVELS], D[M3D_RPN_HEAD_MAX_LEVELS];
-    int n;
-};
-
-struct HcWs {
-    RsHdr hd{};
-    float *dz3c, *s2c, *s1c, *dz2c, *dz1c, *ct, *xg;
-    double* part;
-    unsigned short* w1p;
-    size_t bytes;
-};
-static HcWs hc_ws(void* base, int64_t R, int cap, int npad, int64_t C0, int64_t C1, int64_t C2) {
-    HcWs w{};
-    char* p = static_cast<char*>(base);             // (NULL: the size only)
-    size_t o = 0;
-    auto take = [&](size_t b) { char* q = p ? p + o : nullptr; o += rs_al(b); return q; };
-    char* hdr = take(rs_hdr_bytes(R));
-    if (hdr) w.hd = rs_hdr(hdr, R);
-    w.dz3c = reinterpret_cast<float*>(take(4 * (size_t)cap * npad));
-    w.s2c = reinterpret_cast<float*>(take(4 * (size_t)cap * C2));
-    w.s1c = reinterpret_cast<float*>(take(4 * (size_t)cap * C1));
-    w.dz2c = reinterpret_cast<float*>(take(4 * (size_t)cap * C2));
-    w.dz1c = reinterpret_cast<float*>(take(4 * (size_t)cap * C1));
-    w.w1p = reinterpret_cast<unsigned short*>(take(6 * 27 * (size_t)C0 * C1));
-    w.ct = reinterpret_cast<float*>(take(4 * (size_t)cap * 27 * C0));
-    w.xg = reinterpret_cast<float*>(take(4 * 27 * (size_t)cap * C0));
-    w.part = reinterpret_cast<double*>(take(8 * (size_t)(cap / HC_CHUNK) * C2 * (C1 > npad ? C1 : npad)));
-    w.bytes = o;
-    return w;
-}
-
-// slot[row] = row active (0 / 1), blk[group] = active rows of the group's RS_BLK rows; one thread per
-// row (the rule of rs_lane_active: any element != 0.0f, so -0.0f is not and a NaN is)
-__global__ __launch_bounds__(256) void hc_flag_kernel(const float* __restrict__ dl, const float* __restrict__ db,
-                                                      int R, int nl, int nb, int* __restrict__ blk,
-                                                      int* __restrict__ slot) {
-    const int r = blockIdx.x * 256 + threadIdx.x;
-    bool a = false;
-    if (r < R) {
-        const float* pl = dl + (int64_t)r * nl;
-        const float* pb = db + (int64_t)r * nb;
-        for (int j = 0; j < nl; ++j) a |= pl[j] != 0.0f;
-        for (int j = 0; j < nb; ++j) a |= pb[j] != 0.0f;
-        slot[r] = a ? 1 : 0;
-    }
-    const unsigned long long m = __ballot(a);
-    const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if ((threadIdx.x & 63) == 0 && (int64_t)g * RS_BLK < R) blk[g] = __popcll(m);
-}
-
-// the prefix of rs_pack_kernel over the flags: slot[row] = compact slot or -1, idx[slot] = row
-// (ascending), the count, the levels' first slots and the overflow word.  Every workgroup sums blk
-// itself; a workgroup owns 4 groups of RS_BLK rows.
-__global__ __launch_bounds__(256) void hc_index_kernel(int R, int cap, HcLevels lv, int* __restrict__ h,
-                                                       const int* __restrict__ blk, int* __restrict__ slot,
-                                                       int* __restrict__ idx) {
-    __shared__ int red[2][4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int nblk = (R + RS_BLK - 1) / RS_BLK;
-    const int g0 = blockIdx.x * 4;
-    int tot = 0, pre = 0;
-    for (int i = tid; i < nblk; i += 256) {
-        const int c = blk[i];
-        tot += c;
-        if (i < g0) pre += c;
-    }
-#pragma unroll
-    for (int o = 32; o; o >>= 1) {
-        tot += __shfl_xor(tot, o);
-        pre += __shfl_xor(pre, o);
-    }
-    if (lane == 0) { red[0][wave] = tot; red[1][wave] = pre; }
-    __syncthreads();
-    const int n = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-    const int nn = n < cap ? n : cap;
-    if (blockIdx.x == 0 && tid == 0) {
-        h[RS_STATE] = RS_SPARSE;
-        h[RS_SKIP_DENSE] = 1;
-        h[RS_SKIP_SPARSE] = 0;
-        h[RS_N] = nn;
-        h[RS_PROBE] = 0;
-        h[HC_NRAW] = n;
-        if (n > cap) h[HC_OVERFLOW] += 1;          // sticky: only the caller clears it
-        h[HC_LEVEL0 + lv.n] = nn;
-    }
-    const int g = g0 + wave;
-    if (g >= nblk) return;
-    int base = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-    for (int q = 0; q < wave; ++q) base += blk[g0 + q];
-    const int r = g * RS_BLK + lane;
-    const bool act = r < R && slot[r] != 0;
-    const unsigned long long m = __ballot(act);
-    const int s = base + __popcll(m & ((1ull << lane) - 1ull));    // active rows before r
-    if (r < R) {
-        slot[r] = act && s < cap ? s : -1;
-        if (act && s < cap) idx[s] = r;
-        for (int l = 0; l < lv.n; ++l)
-            if (lv.row0[l] == r) h[HC_LEVEL0 + l] = s < cap ? s : cap;
-    }
-}
-
-__device__ __forceinline__ int hc_level_of(const HcLevels& lv, int row) {
-    int l = 0;
-    while (l + 1 < lv.n && row >= lv.row0[l + 1]) ++l;
-    return l;
-}
-
-// one wave per compact row r: dz3c[r] = [dlogits | dbbox | 0] of row idx[r], s2c[r] / s1c[r] that row
-// of its level's rpn_conv_shared2 / rpn_conv_shared1 output; rows n..cap zero; overflow: dz3c = NaN
-__global__ __launch_bounds__(256) void hc_gather_kernel(const float* __restrict__ dl, const float* __restrict__ db,
-                                                        int nl, int nb, int npad, int cap, int C1, int C2,
-                                                        HcLevels lv, const int* __restrict__ h,
-                                                        const int* __restrict__ idx, float* __restrict__ dz3c,
-                                                        float* __restrict__ s2c, float* __restrict__ s1c) {
-    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= cap) return;
-    const int n = h[HC_NRAW];
-    const bool on = r < n;                         // (overflow: n > cap, every row on)
-    int row = 0, l = 0;
-    if (on) {
-        row = idx[r];
-        l = hc_level_of(lv, row);
-    }
-    if (lane < npad) {
-        float v = 0.0f;
-        if (on && lane < nl) v = dl[(int64_t)row * nl + lane];
-        else if (on && lane < nl + nb) v = db[(int64_t)row * nb + lane - nl];
-        if (n > cap) v = __builtin_nanf("");
-        dz3c[(int64_t)r * npad + lane] = v;
-    }
-    const int64_t local = row - lv.row0[l];
-    rs_copy_row(lv.s2[l] + local * C2, s2c + (int64_t)r * C2, C2, lane, on);
-    rs_copy_row(lv.s1[l] + local * C1, s1c + (int64_t)r * C1, C1, lane, on);
-}
-
-// out[c] += sum over the rows of x [rows][C], in a fixed order: a workgroup owns 64 columns, its 16
-// waves every 16th row each, then the 16 partials in wave order.  (These small reductions keep their
-// running sums in double: a handful of adds per thread, and the compact rows' sums round once.)
-__global__ __launch_bounds__(1024) void hc_colsum_kernel(const float* __restrict__ x, int rows, int C,
-                                                         float* __restrict__ out) {
-    __shared__ double part[16][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = blockIdx.x * 64 + lane;
-    double a = 0.0;
-    if (c < C)
-        for (int r = wave; r < rows; r += 16) a += (double)x[(int64_t)r * C + c];
-    part[wave][lane] = a;
-    __syncthreads();
-    if (wave == 0 && c < C) {
-        double s = part[0][lane];
-        for (int q = 1; q < 16; ++q) s += part[q][lane];
-        out[c] += (float)s;
-    }
-}
-
-// dz2c[r][k] = [s2c[r][k] > 0] sum_j dz3c[r][j] w24[k][j]  (j < n8, ascending)
-__global__ __launch_bounds__(256) void hc_dz2_kernel(const float* __restrict__ dz3c, const float* __restrict__ w24,
-                                                     const float* __restrict__ s2c, int cap, int C2, int n8, int npad,
-                                                     float* __restrict__ dz2c) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (int64_t)cap * C2) return;
-    const int r = (int)(i / C2), k = (int)(i % C2);
-    double a = 0.0;
-    for (int j = 0; j < n8; ++j) a += (double)dz3c[(int64_t)r * npad + j] * (double)w24[(int64_t)k * n8 + j];
-    dz2c[i] = s2c[i] > 0.0f ? (float)a : 0.0f;
-}
-
-// dz1c[r][n] = [s1c[r][n] > 0] sum_k dz2c[r][k] w2[n][k], the running sum in double (k ascending), so
-// each element is the correctly rounded product row: the compact 1x1x1 products are a few hundred MFLOP,
-// and rounding them once keeps the compact chain no further from float64 than the dense launches, whose
-// split GEMM on the same rows differs from it only in its last roundings.  A workgroup owns 16 compact
-// rows x 64 columns n: the rows' dz2c in LDS (256 k at a time), lane = n, wave w rows 4w..4w+3; the
-// lane walks its w2 row in float4s.  Row tiles at or past n store zeros.
-constexpr int HC_DZ1_ROWS = 16;
-__global__ __launch_bounds__(256) void hc_dz1_kernel(const float* __restrict__ dz2c, const float* __restrict__ w2,
-                                                     const float* __restrict__ s1c, int K, int N,
-                                                     const int* __restrict__ h, float* __restrict__ dz1c) {
-    __shared__ __attribute__((aligned(16))) float a[HC_DZ1_ROWS][256];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = blockIdx.x * 64 + lane, r0 = blockIdx.y * HC_DZ1_ROWS;
-    if (r0 >= h[RS_N]) {                            // (uniform over the workgroup)
-        for (int i = 0; i < 4; ++i) dz1c[(int64_t)(r0 + wave * 4 + i) * N + n] = 0.0f;
-        return;
-    }
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int kc = 0; kc < K; kc += 256) {
-        __syncthreads();
-        for (int rr = 0; rr < HC_DZ1_ROWS; ++rr)
-            a[rr][tid] = kc + tid < K ? dz2c[(int64_t)(r0 + rr) * K + kc + tid] : 0.0f;
-        __syncthreads();
-        const int kn = K - kc < 256 ? K - kc : 256;
-        for (int k = 0; k < kn; k += 4) {
-            const float4 wv = *reinterpret_cast<const float4*>(w2 + (int64_t)n * K + kc + k);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float4 x = *reinterpret_cast<const float4*>(&a[wave * 4 + i][k]);
-                acc[i] += (double)x.x * (double)wv.x;
-                acc[i] += (double)x.y * (double)wv.y;
-                acc[i] += (double)x.z * (double)wv.z;
-                acc[i] += (double)x.w * (double)wv.w;
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int64_t o = (int64_t)(r0 + wave * 4 + i) * N + n;
-        dz1c[o] = s1c[o] > 0.0f ? (float)acc[i] : 0.0f;
-    }
-}
-
-// part[chunk][k][j] = sum over the chunk's HC_CHUNK compact rows of A[r][k] B[r][j] (A [cap][K],
-// B [cap][N]; double, rows ascending); a thread owns four consecutive k of one column j.  Chunks at or
-// past n are left out here and in the fold.
-__global__ __launch_bounds__(256) void hc_wg_part_kernel(const float* __restrict__ A, const float* __restrict__ B,
-                                                         int K, int N, const int* __restrict__ h,
-                                                         double* __restrict__ part) {
-    const int r0 = blockIdx.y * HC_CHUNK;
-    if (r0 >= h[RS_N]) return;
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (int64_t)(K / 4) * N) return;
-    const int k = (int)(i / N) * 4, j = (int)(i % N);
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int r = r0; r < r0 + HC_CHUNK; ++r) {
-        const float4 av = *reinterpret_cast<const float4*>(A + (int64_t)r * K + k);
-        const double b = (double)B[(int64_t)r * N + j];
-        acc[0] += (double)av.x * b;
-        acc[1] += (double)av.y * b;
-        acc[2] += (double)av.z * b;
-        acc[3] += (double)av.w * b;
-    }
-    double* o = part + ((int64_t)blockIdx.y * K + k) * N + j;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) o[(int64_t)q * N] = acc[q];
-}
-
-// dw[i] += sum over the chunks that hold an active row, in chunk order
-__global__ __launch_bounds__(256) void hc_wg_reduce_kernel(const double* __restrict__ part, int kn,
-                                                           const int* __restrict__ h, float* __restrict__ dw) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const int chunks = (h[RS_N] + HC_CHUNK - 1) / HC_CHUNK;
-    if (i >= kn || chunks == 0) return;
-    double s = part[i];
-    for (int q = 1; q < chunks; ++q) s += part[(int64_t)q * kn + i];
-    dw[i] += (float)s;
-}
-
-// xg[tap][r] = the tap's input row of compact row r (the tap gather of rs_pack_kernel, on the level
-// of idx[r]; 'same' padding: zero outside; rows n..cap zero), one wave per compact row
-__global__ __launch_bounds__(256) void hc_xg_kernel(HcLevels lv, int cap, int C, const int* __restrict__ h,
-                                                    const int* __restrict__ idx, float* __restrict__ xg) {
-    const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= cap) return;
-    const bool on = r < h[RS_N];
-    int H = 1, W = 1, D = 1, yo = 0, xo = 0, zo = 0;
-    const float* x = lv.p[0];
-    if (on) {
-        const int row = idx[r], l = hc_level_of(lv, row);
-        int t = row - lv.row0[l];
-        H = lv.H[l]; W = lv.W[l]; D = lv.D[l];
-        x = lv.p[l];
-        zo = t % D; t /= D;
-        xo = t % W;
-        yo = t / W;
-    }
-    for (int c = lane * 4; c < C; c += 256) {
-        float4 v[27];
-#pragma unroll
-        for (int tap = 0; tap < 27; ++tap) {
-            const int yi = yo + tap / 9 - 1, xi = xo + (tap / 3) % 3 - 1, zi = zo + tap % 3 - 1;
-            const bool in = on && (unsigned)yi < (unsigned)H && (unsigned)xi < (unsigned)W && (unsigned)zi < (unsigned)D;
-            v[tap] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (in) v[tap] = *reinterpret_cast<const float4*>(x + (((int64_t)yi * W + xi) * D + zi) * C + c);
-        }
-#pragma unroll
-        for (int tap = 0; tap < 27; ++tap)
-            *reinterpret_cast<float4*>(xg + ((int64_t)tap * cap + r) * C + c) = v[tap];
-    }
-}
-
-// the argument checks of both entry points (no launch before them) and the level table
-static int hc_check(const m3d_rpn_head_bwd_t* a, bool weight, HcLevels& lv, int64_t& R, int& npad) {
-    if (!a) return einval("rpn_head_compact: NULL argument block");
-    if (a->nlevels < 1 || a->nlevels > M3D_RPN_HEAD_MAX_LEVELS)
-        return einval("rpn_head_compact: nlevels must be in [1, 8]");
-    if (a->apl < 1 || 8 * a->apl > 64) return einval("rpn_head_compact: apl must be in [1, 8]");
-    if (a->cap < 256 || a->cap > RS_CAP_MAX || a->cap % 256)
-        return einval("rpn_head_compact: cap must be a multiple of 256 in [256, 4096]");
-    if (a->C0 <= 0 || a->C1 <= 0 || a->C2 <= 0 || a->C0 % 64 || a->C1 % 64 || a->C2 % 64 || a->C0 > 4096 ||
-        a->C1 > 4096 || a->C2 > 4096)
-        return einval("rpn_head_compact: channel counts must be multiples of 64 in [64, 4096]");
-    if ((int64_t)a->cap * 27 * a->C0 * 4 >= 0xFFFFFFF0LL || 27 * a->C0 * a->C1 * 2 >= 0xFFFFFFF0LL)
-        return einval("rpn_head_compact: operand larger than 4 GiB (32-bit buffer offsets)");
-    npad = (8 * a->apl + 31) / 32 * 32;
-    R = 0;
-    lv = HcLevels{};
-    lv.n = a->nlevels;
-    for (int l = 0; l < a->nlevels; ++l) {
-        const m3d_rpn_head_level_t& q = a->levels[l];
-        if (q.H <= 0 || q.W <= 0 || q.D <= 0) return einval("rpn_head_compact: level extents must be positive");
-        if (!q.p || !q.s1 || !q.s2 || (!weight && !q.dp)) return einval("rpn_head_compact: NULL level pointer");
-        if (!weight && (q.accumulate & ~1)) return einval("rpn_head_compact: accumulate must be 0 or 1");
-        lv.p[l] = q.p; lv.s1[l] = q.s1; lv.s2[l] = q.s2;
-        lv.H[l] = q.H; lv.W[l] = q.W; lv.D[l] = q.D;
-        lv.row0[l] = (int)R;
-        R += (int64_t)q.H * q.W * q.D;
-        if (R > 0x7FFFFFFF / 64) return einval("rpn_head_compact: more than 2^25 voxel rows");
-    }
-    lv.row0[a->nlevels] = (int)R;
-    if (!a->workspace || a->ws_bytes < m3d_rpn_head_compact_workspace_bytes(R, a->cap, a->apl, a->C0, a->C1, a->C2))
-        return einval("rpn_head_compact: workspace missing or too small");
-    if (weight) {
-        if (!a->dw1 || !a->dw2 || !a->dw24) return einval("rpn_head_compact: NULL weight gradient");
-    } else if (!a->dlogits || !a->dbbox || !a->w1 || !a->w2 || !a->w24 || !a->db1 || !a->db2 || !a->db24) {
-        return einval("rpn_head_compact: NULL pointer");
-    } else if (reinterpret_cast<uintptr_t>(a->w2) & 15) {
-        return einval("rpn_head_compact: w2 must be 16-byte aligned");
-    }
-    return M3D_OK;
-}
-
-extern "C" size_t m3d_rpn_head_compact_workspace_bytes(int64_t rows, int32_t cap, int32_t apl, int64_t C0,
-                                                       int64_t C1, int64_t C2) {
-    if (rows <= 0 || rows > 0x7FFFFFFF / 64 || cap < 256 || cap > RS_CAP_MAX || cap % 256 || apl < 1 || apl > 8 ||
-        C0 <= 0 || C1 <= 0 || C2 <= 0 || C0 > 4096 || C1 > 4096 || C2 > 4096)
-        return 0;
-    return hc_ws(nullptr, rows, cap, (8 * apl + 31) / 32 * 32, C0, C1, C2).bytes;
-}
-
-// scan, gather, the 1x1x1 chain's data path with its bias sums, and rpn_conv_shared1's data gradient
-extern "C" int m3d_rpn_head_compact_bwd_data(const m3d_rpn_head_bwd_t* a, m3d_stream_t s_) {
-    HcLevels lv{};
-    int64_t R;
-    int npad;
-    if (int rc = hc_check(a, false, lv, R, npad)) return rc;
-    hipStream_t s = st(s_);
-    const int cap = a->cap, nl = 2 * a->apl, nb = 6 * a->apl;
-    const int C0 = (int)a->C0, C1 = (int)a->C1, C2 = (int)a->C2;
-    const HcWs w = hc_ws(a->workspace, R, cap, npad, C0, C1, C2);
-    const int nblk = (int)((R + RS_BLK - 1) / RS_BLK);
-    hipLaunchKernelGGL(hc_flag_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s, a->dlogits, a->dbbox, (int)R,
-                       nl, nb, w.hd.blk, w.hd.slot);
-    hipLaunchKernelGGL(hc_index_kernel, dim3((unsigned)((nblk + 3) / 4)), dim3(256), 0, s, (int)R, cap, lv, w.hd.h,
-                       w.hd.blk, w.hd.slot, w.hd.idx);
-    hipLaunchKernelGGL(hc_gather_kernel, dim3((unsigned)(cap / 4)), dim3(256), 0, s, a->dlogits, a->dbbox, nl, nb, npad,
-                       cap, C1, C2, lv, w.hd.h, w.hd.idx, w.dz3c, w.s2c, w.s1c);
-    // rpn_class_raw + rpn_bbox_pred: bias sums, dz2c = (dz3c w24^T) [s2c > 0]
-    hipLaunchKernelGGL(hc_colsum_kernel, dim3(1), dim3(1024), 0, s, w.dz3c, cap, npad, a->db24);
-    hipLaunchKernelGGL(hc_dz2_kernel, dim3(grid_for((int64_t)cap * C2, 256)), dim3(256), 0, s, w.dz3c, a->w24, w.s2c,
-                       cap, C2, nl + nb, npad, w.dz2c);
-    hipLaunchKernelGGL(hc_colsum_kernel, dim3((unsigned)(C2 / 64)), dim3(1024), 0, s, w.dz2c, cap, C2, a->db2);
-    // rpn_conv_shared2: dz1c = (dz2c w2^T) [s1c > 0]
-    hipLaunchKernelGGL(hc_dz1_kernel, dim3((unsigned)(C1 / 64), (unsigned)(cap / HC_DZ1_ROWS)), dim3(256), 0, s, w.dz2c,
-                       a->w2, w.s1c, C2, C1, w.hd.h, w.dz1c);
-    hipLaunchKernelGGL(hc_colsum_kernel, dim3((unsigned)(C1 / 64)), dim3(1024), 0, s, w.dz1c, cap, C1, a->db1);
-    // rpn_conv_shared1: ct[r][tap * C0 + c] = sum_n dz1c[r][n] w1[tap][c][n] (row tiles past n return),
-    // then every level's dx from its slice of slot
-    const int64_t nw = (int64_t)27 * C0 * C1;
-    hipLaunchKernelGGL(split3_kernel, dim3(grid_for(nw, 256)), dim3(256), 0, s, a->w1, nw, w.w1p);
-    WinoWs g{};
-    g.U = w.dz1c;
-    g.V = reinterpret_cast<float*>(w.w1p);
-    g.M = w.ct;
-    wino_gemm_x3(g, cap, C1, 27 * C0, 1, s, true, nullptr, w.hd.h + RS_N);
-    for (int l = 0; l < lv.n; ++l) {
-        const int64_t nvox = (int64_t)lv.H[l] * lv.W[l] * lv.D[l];
-        hipLaunchKernelGGL(rs_dgrad_out_kernel, dim3((unsigned)((nvox + RS_VOX - 1) / RS_VOX)), dim3(256), 0, s, w.ct,
-                           nvox, lv.H[l], lv.W[l], lv.D[l], lv.D[l], 1, C0, a->levels[l].accumulate, w.hd.h,
-                           w.hd.slot + lv.row0[l], a->levels[l].dp);
-    }
-    return check_launch("rpn_head_compact_bwd_data");
-}
-
-// the three weight gradients, from the compact matrices m3d_rpn_head_compact_bwd_data left in the
-// workspace (enqueued after it: the same stream, or one that waits for it)
-extern "C" int m3d_rpn_head_compact_bwd_weight(const m3d_rpn_head_bwd_t* a, const m3d_det_t* det, m3d_stream_t s_) {
-    M3D_DET_SCOPE(det);
-    HcLevels lv{};
-    int64_t R;
-    int npad;
-    if (int rc = hc_check(a, true, lv, R, npad)) return rc;
-    hipStream_t s = st(s_);
-    const int cap = a->cap, C0 = (int)a->C0, C1 = (int)a->C1, C2 = (int)a->C2;
-    const HcWs w = hc_ws(a->workspace, R, cap, npad, C0, C1, C2);
-    // dw24 += s2c^T dz3c, dw2 += s1c^T dz2c: chunk partials, then the chunks in order
-    const unsigned chunks = (unsigned)(cap / HC_CHUNK);
-    hipLaunchKernelGGL(hc_wg_part_kernel, dim3(grid_for((int64_t)(C2 / 4) * npad, 256), chunks), dim3(256), 0, s, w.s2c,
-                       w.dz3c, C2, npad, w.hd.h, w.part);
-    hipLaunchKernelGGL(hc_wg_reduce_kernel, dim3(grid_for((int64_t)C2 * npad, 256)), dim3(256), 0, s, w.part, C2 * npad,
-                       w.hd.h, a->dw24);
-    hipLaunchKernelGGL(hc_wg_part_kernel, dim3(grid_for((int64_t)(C1 / 4) * C2, 256), chunks), dim3(256), 0, s, w.s1c,
-                       w.dz2c, C1, C2, w.hd.h, w.part);
-    hipLaunchKernelGGL(hc_wg_reduce_kernel, dim3(grid_for((int64_t)C1 * C2, 256)), dim3(256), 0, s, w.part, C1 * C2,
-                       w.hd.h, a->dw2);
-    // dw1[tap] += xg[tap]^T dz1c
-    hipLaunchKernelGGL(hc_xg_kernel, dim3((unsigned)(cap / 4)), dim3(256), 0, s, lv, cap, C0, w.hd.h, w.hd.idx, w.xg);
-    const int fe = launch_wgrad_x3(w.xg, w.dz1c, a->dw1, cap, C0, C1, 27, (int64_t)cap * C0, 0, (int64_t)C0 * C1, s);
-    if (fe) {
-        set_error("rpn_head_compact_bwd_weight: %s", hipGetErrorString((hipError_t)fe));
-        return M3D_EHIP;
-    }
-    return check_launch("rpn_head_compact_bwd_weight");
 }

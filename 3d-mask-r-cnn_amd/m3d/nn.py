@@ -1686,7 +1686,7 @@ class _RPNOut(torch.autograd.Function):
         return (None, None, None, None, None) + tuple(dshared)
 
 
-# The RPN head's backward on the sampled anchors' rows only (csrc/conv3d.hip,
+# The RPN head's backward on the sampled anchors' rows only (csrc/rpn_head_bwd.hip,
 # m3d_rpn_head_compact_bwd_data / _bwd_weight): the active rows are
 # found once from the loss gradient and rpn_class_raw / rpn_bbox_pred,
 # rpn_conv_shared2 and rpn_conv_shared1 run their backward on compact [cap][C]

@@ -619,7 +619,7 @@ int m3d_conv3d_bwd_data_splitk_bn(const float* dz, const float* w, int64_t B, in
  * C[b] = act(A[b] B[b] + bias) (+ C[b] if accumulate); A [M][K], B [K][N],
  * C [M][N] row-major, batches contiguous; N multiple of 4.  The Winograd
  * point-wise products above do not run it: they run the x3_gemm kernels on
- * the exact bf16 split (conv3d.hip). */
+ * the exact bf16 split (conv3d.hip; split3 in conv_types.h). */
 int m3d_gemm_f32(const float* A, const float* B, float* C, int64_t batch, int64_t M, int64_t K,
                  int64_t N, const float* bias, int32_t relu, int32_t accumulate, m3d_stream_t s);
 

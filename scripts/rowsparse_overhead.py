@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Per-call time of the Winograd backward with the row-sparse attempt off (rs_mode 1), as the library
 decides (0) and forced (2), on dense and sparse dz at the 128^3 step's shapes: the measurement behind
-RS_MIN_FLOP (csrc/conv3d.hip) and DESIGN.md 5, kept as profiles/rowsparse_overhead.txt.  HIP-event time
+RS_MIN_FLOP (csrc/conv_rowsparse.hip) and DESIGN.md 5, kept as profiles/rowsparse_overhead.txt.  HIP-event time
 of 20 back-to-back calls after 5 warm-ups, median (min, max) of 5 such batches.  state: what the data
 gradient's scan decided, [state (1 dense, 2 sparse), skip_dense, skip_sparse, n]; "-": no scan ran.
 

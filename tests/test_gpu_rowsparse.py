@@ -1,4 +1,4 @@
-"""The row-sparse path of the Winograd backward entry points (csrc/conv3d.hip,
+"""The row-sparse path of the Winograd backward entry points (csrc/conv3d.hip, csrc/conv_rowsparse.hip,
 "row-sparse output gradients"): the device-side scan of dz, the sparse data and
 weight gradients against the float64 references of tests/convref.py, the
 fallbacks, graph replay and the RPN step.

@@ -1,4 +1,4 @@
-"""m3d_rpn_head_compact_bwd_data / _bwd_weight (csrc/conv3d.hip, "the RPN head's
+"""m3d_rpn_head_compact_bwd_data / _bwd_weight (csrc/rpn_head_bwd.hip, "the RPN head's
 backward on the sampled anchors' rows") against the float64 restatement of
 tests/headref.py, and the route through backbone.RPNHead against the dense one.
 

@@ -1,7 +1,7 @@
 """fp32-class accuracy of the bf16-split ("x3") GEMMs and the Winograd chain.
 
 Every hot GEMM here runs fp32 arithmetic as six bf16 MFMAs on an exact 3-way
-split (csrc/conv3d.hip: split3, x3_mac, x3_mac_pair).  The other GPU tests hold
+split (csrc/conv_types.h: split3; csrc/conv3d.hip: x3_mac, x3_mac_pair).  The other GPU tests hold
 those kernels to 1e-4 .. 1e-5 of max|ref|, far above the ~1e-6 a lost
 second-order term costs (a dropped or doubled MFMA, a wrong plane in a
 hand-interleaved chain, a transform that leaves a lo plane zero).  Three bars

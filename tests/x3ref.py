@@ -2,7 +2,7 @@
 Winograd chain (tests/test_x3ref.py on the CPU, tests/test_gpu_x3_accuracy.py
 on the GPU).  Plain numpy, float64 arrays holding fp32 / bf16 values.
 
-* split3: the kernels' exact 3-way bf16 split (csrc/conv3d.hip, split3).
+* split3: the kernels' exact 3-way bf16 split (csrc/conv_types.h, split3).
 * gemm_x3: C = A B as the kernels sum it -- per 16-deep k step the six bf16
   MFMAs (lo,hi) (mid,mid) (hi,lo) (mid,hi) (hi,mid) (hi,hi), each rounding into
   one fp32 accumulator -- with mutation switches (a dropped or duplicated term,
