@@ -24,88 +24,15 @@
 // + residual (same shape or (2,2,1)-upsampled FPN source), ReLU, strided /
 // channel-split stores (RPN class|bbox heads write their concatenated outputs
 // directly).
+//
+// The one-channel 7^3 stem (stem_*_kernel), which the direct entry points
+// below reach through stem_ok / launch_stem / launch_stem_wgrad, is in
+// conv_stem.hip; the row-sparse and RPN-head backward code in
+// conv_rowsparse.hip and rpn_head_bwd.hip (conv_types.h).
 #include "conv_types.h"
 #include <stdlib.h>
 
 namespace m3d {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
-struct ConvP {
-    const float* a;   // A source (x or dz), channels-last [B,H,W,D,C]
-    int B, H, W, D, C;
-    int OH, OW, OD;   // M grid
-    int kh, kw, kd;
-    int sy, sx, sz;
-    int py, px, pz;
-    int64_t M;
-    int K;            // taps * C
-    const float* w;
-    int N;
-    int flip;         // bwd-data: use tap (taps-1-t)
-    // batched GEMMs (Winograd points): blockIdx.z selects the batch; A, W and Y
-    // advance by these element strides (0 for ordinary convs)
-    int64_t bsa, bsw, bsy;
-    int dly = 1, dlx = 1, dlz = 1;   // dilation (mrcnn_mask_conv3b: fwd, bwd-data on the flipped taps, bwd-weight)
-    int nbatch = 1;                  // batches (PERSIST: looped inside the grid)
-    // depth-slab halo planes beside the slab (the stem and the direct weight
-    // gradient, m3d_conv3d_*_halo): the conv runs on the virtual z grid
-    // [lower halo (hnlo planes) | slab (hdl) | upper halo], D = its depth; x (a)
-    // holds the slab [B,H,W,hdl,C], halo [B,H,W,2*hr,C] the neighbours' planes
-    // ([0,hr) from below, [hr,2hr) from above)
-    const float* halo = nullptr;
-    int hnlo = 0, hdl = 0, hr = 0;
-};
-
-struct Epi {
-    const float* bias;
-    const float* scale;
-    const float* shift;
-    const float* res;
-    int res_mode;
-    int relu;
-    float* z;
-    float* y;
-    int64_t ldy;
-    float* y2;
-    int64_t ldy2;
-    int split;
-    int YH, YW, YD;
-    int ysy, ysx, ysz;
-    int accumulate;
-    int simple;       // y row == m (same grid, unit store stride)
-    // depth-slab halo (wino_output_kernel<.., HALO>): output z over the
-    // halo-extended grid; planes [hlo, hlo + dl) go to y (depth dl), the halo
-    // planes to yh [B][H][W][2][N] (plane 0 below, 1 above)
-    float* yh;
-    int hlo, dl;
-    int deconv = 0;   // > 0: 2x2x2 stride-2 transposed conv, n = tap * deconv + o
-    // fused BN-ReLU backward of the unit that produced this data gradient's
-    // input (m3d_conv3d_bwd_data_bn): the stored value t (after accumulate) is
-    // the unit's output gradient; written instead are dz = act'(t) * scale
-    // (into y), dpre = act'(t) (into fdres, if set), and per-tile channel sums
-    // of dpre, dpre * xhat, dz (rows of fpart, [3][rows][N]) -- the maths of
-    // bn_act_bwd_kernel
-    int fbn = 0, frelu = 0;
-    const float* fy = nullptr;
-    const float* fz = nullptr;
-    const float* fscale = nullptr;
-    const float* fmean = nullptr;
-    const float* frstd = nullptr;
-    float* fdres = nullptr;
-    float* fpart = nullptr;
-    int64_t fprows = 0;           // partial rows (stride of the three sum planes)
-};
-
-
-
-// activation codes (Epi::relu): 0 none, 1 ReLU, 2 sigmoid (mrcnn_mask)
-__device__ __forceinline__ float act(int code, float v) {
-    if (code == 1) return v > 0.0f ? v : 0.0f;
-    if (code == 2) return 1.0f / (1.0f + expf(-v));
-    return v;
-}
 
 // Raw buffer loads: 32-bit byte offsets, and an out-of-range offset returns 0
 // -- used for the implicit zero padding of im2col so the loaders are
@@ -292,11 +219,6 @@ __device__ __forceinline__ void epi_store(const ConvP& p, const Epi& e, int64_t 
     }
 }
 
-// Four consecutive output channels n..n+3 of row m (same op order as epi_store,
-// element-wise): 16-byte loads / stores when the row strides allow it.
-__device__ __forceinline__ float4 ld4(const float* q) { return *reinterpret_cast<const float4*>(q); }
-__device__ __forceinline__ void st4(float* q, const float4& v) { *reinterpret_cast<float4*>(q) = v; }
-
 // The fused BN-act backward of four channels n..n+3 of row m (simple rows):
 // bn_act_bwd_kernel's per-element maths, sums accumulated in s[3][4].  The
 // caller loads y4 / z4 (and the channel's scale / mean / rstd in bn[3]) ahead
@@ -326,6 +248,8 @@ __device__ __forceinline__ void epi_bnbwd4(const Epi& e, int64_t m, int n, float
     if (e.fdres) st4(e.fdres + off, make_float4(g[0], g[1], g[2], g[3]));
 }
 
+// Four consecutive output channels n..n+3 of row m (same op order as epi_store,
+// element-wise): 16-byte loads / stores when the row strides allow it.
 __device__ __forceinline__ void epi_store4(const ConvP& p, const Epi& e, int64_t m, int n, float4 v) {
     if (e.split > 0 || (e.ldy & 3)) {
         epi_store(p, e, m, n, v.x);
@@ -896,33 +820,8 @@ __global__ __launch_bounds__(256, BK == 64 ? 1 : (NBUF == 1 && !FBN ? 3 : 2)) vo
 }
 
 // -------------------------------------------------------------------------
-// Weight-gradient epilogue target.  Default: fp32 atomics into C (the m-splits
-// of a tile arrive in any order, so the last bits vary run to run).
-// Deterministic mode (m3d_set_deterministic): each split stores its tile into
-// part[split][batch][K][N] of the registered scratch and wg_reduce_kernel adds
-// the splits to C in split order; with a single split (the scratch too small
-// for two), the one writer of each element adds to C without an atomic.
-// Store (either mode): the caller declared C uninitialised scratch (`fresh`,
-// the Winograd-domain dW_hat) and the launcher settled on one split of a
-// non-stream-K grid, so each (batch, k, n) has exactly one writer, which
-// stores its sum: no zero-fill before the launch and no read of C
-// (wg_settle).  Every other fresh launch is preceded by the fill.
+// Weight-gradient epilogue target (WgOut, conv_types.h)
 // -------------------------------------------------------------------------
-struct WgOut {
-    float* part;
-    int64_t pstride;      // floats per split (nbatch * K * N)
-    int plain;
-    int store;
-    const int* gate;      // row-sparse gate (bwd_weight_wino): the workgroup returns when *gate != 0; NULL: ungated
-};
-
-__device__ __forceinline__ void wg_put(const WgOut& o, float* C, float* P, int64_t idx, float v) {
-    if (P) P[idx] = v;
-    else if (o.store) C[idx] = v;
-    else if (o.plain) C[idx] += v;
-    else unsafeAtomicAdd(C + idx, v);
-}
-
 // C[b*bsc + r] += sum_{s = 0..splits-1} part[s][b][r]  (r < K*N), summed in s order
 __global__ __launch_bounds__(256) void wg_reduce_kernel(const float* __restrict__ part, int splits,
                                                         int64_t pstride, int64_t kn, int64_t bsc,
@@ -938,7 +837,7 @@ __global__ __launch_bounds__(256) void wg_reduce_kernel(const float* __restrict_
 
 // deterministic-mode target for `splits` m-splits of an nbatch x K x N gradient
 // (splits may be lowered to what the scratch holds)
-static WgOut wg_out(int64_t& splits, int64_t nbatch, int64_t K, int64_t N) {
+WgOut wg_out(int64_t& splits, int64_t nbatch, int64_t K, int64_t N) {
     WgOut o{nullptr, 0, 0, 0};
     const DetState d = det();
     if (!d.on) return o;
@@ -955,8 +854,8 @@ static WgOut wg_out(int64_t& splits, int64_t nbatch, int64_t K, int64_t N) {
     return o;
 }
 
-static void wg_finish(const WgOut& o, int64_t splits, int64_t nbatch, int64_t K, int64_t N, int64_t bsc,
-                      float* C, hipStream_t s) {
+void wg_finish(const WgOut& o, int64_t splits, int64_t nbatch, int64_t K, int64_t N, int64_t bsc,
+               float* C, hipStream_t s) {
     if (!o.part) return;
     hipLaunchKernelGGL(wg_reduce_kernel, dim3(grid_for(o.pstride, 256)), dim3(256), 0, s, o.part, (int)splits,
                        o.pstride, K * N, nbatch > 1 ? bsc : K * N, C, o.gate);
@@ -1182,7 +1081,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(ConvP p, const float
 // ------------------------------------------------------------------ dispatch
 // CUs of the calling thread's current device, asked per call (the runtime
 // answers from its device table): nothing is cached across calls or devices
-static int num_cus() {
+int num_cus() {
     int dev = 0, n = 0;
     (void)hipGetDevice(&dev);
     if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
@@ -3462,301 +3361,6 @@ extern "C" int m3d_deconv3d_k2s2(const float* x, int64_t B, int64_t H, int64_t W
     e.ysy = e.ysx = e.ysz = 1; e.simple = 0; e.deconv = (int)Cout;
     dispatch_gemm<true, true>(p, e, st(s));
     return check_launch("conv_gemm_kernel(deconv)");
-}
-
-// ---- the one-channel 7^3 stem: conv1 (core/models.py:242, Conv3D(64, (7,7,7),
-// strides (2,2,1)) after ZeroPadding3D(3)) -------------------------------------
-// The implicit GEMM's scalar loader reaches 0.27 of the f32 MFMA peak here
-// (K = 343 taps of ONE channel: no channel vector to load).  This kernel keeps
-// the whole K operand on chip: the 343 x 64 weights live in LDS for the life
-// of a workgroup that loops over many tiles (about 4 per CU), and every wave owns one
-// output column (oy, ox) x 32 z x 64 channels with its own input window (the
-// 49 (ky, kx) rows x 38 z voxels, + one zero row) in its own LDS region,
-// refilled from registers prefetched during the previous tile's MFMAs.  No
-// barrier after the weight load: the waves of a CU run out of phase.
-// K order: the two MFMA k-slots (lane halves h) walk (ky, kx) rows R = rp and
-// R = rp + 25 in step, 7 taps kz each -- so a lane's window offset is
-// R * 38 + kz: one add per row, the 7 taps as ds_read immediates (a
-// per-tap index walk cost more issue than the MFMAs).  Row R = 49 is the
-// padding (zero weights, zero window row).  Epilogue: each 32-channel
-// accumulator is staged in the wave's LDS region (row stride 40 floats:
-// the lane halves, 4 rows apart, land 32 banks apart) and leaves as
-// row-contiguous float4s through epi_store4 (bias, z, frozen BN, ReLU).
-// Summation order: K in the (R pair, kz) order above -- an exact f32 FMA
-// chain, a different order than the implicit GEMM (parity 1e-4).
-constexpr int STEM_TZ = 32;
-constexpr int STEM_WZ = STEM_TZ + 6;                             // 38
-constexpr int STEM_WIN = 50 * STEM_WZ;                           // 49 rows + the zero row: 1900 floats
-constexpr int STEM_RP = 25;                                      // row pairs (R, R + 25)
-constexpr int STEM_NP = STEM_RP * 7;                             // 175 k pairs
-constexpr int STEM_PER = (49 * STEM_WZ + 63) / 64;               // window values per lane (30)
-constexpr int STEM_SLD = 40;                                     // epilogue staging row stride
-
-__global__ __launch_bounds__(512) void stem_fwd_kernel(ConvP p, Epi e, int tz_n, int64_t ntiles) {
-    __shared__ float wsh[STEM_NP * 128];          // [pair][h*32+l32][nb]  (89.6 KB)
-    __shared__ float win[8][STEM_WIN];            // one window / staging region per wave (60.8 KB)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l32 = lane & 31, h = lane >> 5;
-    for (int i = tid; i < STEM_NP * 128; i += 512) {
-        const int kp = i >> 7, r = i & 127, nb = r & 1, hl = r >> 1, hh = hl >> 5, ll = hl & 31;
-        const int R = kp / 7 + STEM_RP * hh, kz = kp % 7;
-        wsh[i] = R < 49 ? p.w[(R * 7 + kz) * 64 + nb * 32 + ll] : 0.0f;
-    }
-    float* ww = win[wave];
-    if (lane < STEM_WZ) ww[49 * STEM_WZ + lane] = 0.0f;   // the padding row
-    __syncthreads();                              // the only barrier: waves run free below
-    const size_t plane = (size_t)(p.halo ? p.hdl : p.D), row = (size_t)p.W * plane, img = (size_t)p.H * row;
-    auto decode = [&](int64_t t, int& b, int& oy, int& ox, int& tz) {
-        tz = (int)(t % tz_n); t /= tz_n;
-        ox = (int)(t % p.OW); t /= p.OW;
-        oy = (int)(t % p.OH);
-        b = (int)(t / p.OH);
-    };
-    auto fetch = [&](int64_t tile, float* v) {
-        int b, oy, ox, tz;
-        decode(tile, b, oy, ox, tz);
-        const int gy0 = 2 * oy - p.py, gx0 = 2 * ox - p.px, gz0 = tz * STEM_TZ - p.pz;
-        const float* xb = p.a + b * img;
-#pragma unroll
-        for (int q = 0; q < STEM_PER; ++q) {
-            const int i = lane + 64 * q;
-            float val = 0.0f;
-            if (i < 49 * STEM_WZ) {
-                const int R = i / STEM_WZ, iz = i - R * STEM_WZ;
-                const int gy = gy0 + R / 7, gx = gx0 + R % 7, gz = gz0 + iz;
-                if (gy >= 0 && gy < p.H && gx >= 0 && gx < p.W && gz >= 0 && gz < p.D) {
-                    if (p.halo) {     // virtual z grid: slab planes from x, the others from the halo
-                        const int zl = gz - p.hnlo;
-                        if ((unsigned)zl < (unsigned)p.hdl)
-                            val = xb[gy * row + gx * plane + zl];
-                        else
-                            val = p.halo[(((size_t)b * p.H + gy) * p.W + gx) * (2 * p.hr) +
-                                         (zl < 0 ? zl + p.hr : p.hr + zl - p.hdl)];
-                    } else {
-                        val = xb[gy * row + gx * plane + gz];
-                    }
-                }
-            }
-            v[q] = val;
-        }
-    };
-    const int64_t w0 = (int64_t)blockIdx.x * 8 + wave, wstride = (int64_t)gridDim.x * 8;
-    float4 ebias[2], escale[2], eshift[2];
-    for (int nb = 0; nb < 2; ++nb) {
-        const int n = nb * 32 + 4 * (lane & 7);
-        ebias[nb] = e.bias ? ld4(e.bias + n) : make_float4(0.f, 0.f, 0.f, 0.f);
-        escale[nb] = e.scale ? ld4(e.scale + n) : make_float4(1.f, 1.f, 1.f, 1.f);
-        eshift[nb] = e.scale ? ld4(e.shift + n) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    float pre[STEM_PER];
-    if (w0 < ntiles) fetch(w0, pre);
-    for (int64_t tile = w0; tile < ntiles; tile += wstride) {
-#pragma unroll
-        for (int q = 0; q < STEM_PER; ++q)
-            if (lane + 64 * q < 49 * STEM_WZ) ww[lane + 64 * q] = pre[q];
-        __builtin_amdgcn_wave_barrier();
-        if (tile + wstride < ntiles) fetch(tile + wstride, pre);      // next window in flight
-        int b, oy, ox, tz;
-        decode(tile, b, oy, ox, tz);
-        floatx16 acc0 = {}, acc1 = {};
-        const float* wa = ww + STEM_RP * STEM_WZ * h + l32;           // row R = rp + 25 h
-        const float* wb = wsh + lane * 2;
-        for (int rp = 0; rp < STEM_RP; ++rp) {
-#pragma unroll
-            for (int kz = 0; kz < 7; ++kz) {
-                const float a = wa[kz];
-                const float2 bv = *reinterpret_cast<const float2*>(wb + kz * 128);
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bv.x, acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bv.y, acc1, 0, 0, 0);
-            }
-            wa += STEM_WZ;
-            wb += 7 * 128;
-        }
-        __builtin_amdgcn_wave_barrier();          // window reads done before the staging writes
-        const int64_t mbase = (((int64_t)b * p.OH + oy) * p.OW + ox) * p.OD;
-        const int oz0 = tz * STEM_TZ;
-#pragma unroll
-        for (int nb = 0; nb < 2; ++nb) {
-            const floatx16& acc = nb ? acc1 : acc0;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) ww[((r & 3) + 8 * (r >> 2) + 4 * h) * STEM_SLD + l32] = acc[r];
-            __builtin_amdgcn_wave_barrier();
-            // a lane's 4 channels are the same in every row it stores (c4 = lane & 7):
-            // the epilogue parameters are held in registers (epi_store4's order of ops)
-            const int n = nb * 32 + 4 * (lane & 7);
-            const float4 bb = ebias[nb], sc = escale[nb], sh = eshift[nb];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {                 // 32 rows x 8 float4 = 4 per lane
-                const int rr = (lane >> 3) + 8 * q;
-                float4 v = *reinterpret_cast<const float4*>(ww + rr * STEM_SLD + 4 * (lane & 7));
-                if (oz0 + rr >= p.OD) continue;
-                const int64_t m = mbase + oz0 + rr;
-                if (e.bias) { v.x += bb.x; v.y += bb.y; v.z += bb.z; v.w += bb.w; }
-                if (e.z) st4(e.z + m * 64 + n, v);
-                if (e.scale) {
-                    v.x = v.x * sc.x + sh.x; v.y = v.y * sc.y + sh.y;
-                    v.z = v.z * sc.z + sh.z; v.w = v.w * sc.w + sh.w;
-                }
-                if (e.relu) {
-                    v.x = act(e.relu, v.x); v.y = act(e.relu, v.y); v.z = act(e.relu, v.z); v.w = act(e.relu, v.w);
-                }
-                st4(e.y + m * 64 + n, v);
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-    }
-}
-
-
-static bool stem_ok(int64_t Cin, int kh, int kw, int kd, int64_t Cout, int sy, int sx, int sz, int dly, int dlx,
-                    int dlz, int res_mode, int64_t split_n, int64_t ldy) {
-    // the kernel's own epilogue covers bias / z / frozen BN / activation, plain
-    // [M, 64] stores (no residual, split or accumulate)
-    return Cin == 1 && kh == 7 && kw == 7 && kd == 7 && Cout == 64 && sy == 2 && sx == 2 && sz == 1 &&
-           dly == 1 && dlx == 1 && dlz == 1 && res_mode == 0 && split_n <= 0 && (ldy <= 0 || ldy == 64);
-}
-
-// ---- the stem's weight gradient: dW[343][64] += sum_m window(m)[tap] dz[m][ch] ----
-// The implicit-GEMM weight gradient reads the one-channel window through its
-// scalar loader (0.27 of the f32 MFMA peak).  Here a workgroup (8 waves) loops
-// over a contiguous range of m-tiles (one output column (oy, ox) x 32 z); per
-// tile the 49 x 38 input window (the same fetch as stem_fwd_kernel, halo planes
-// included) and the 32 x 64 dz rows are staged in LDS (double-buffered, one
-// barrier per tile) and every wave accumulates its 11 of the 88 16 x 16 dW
-// tiles (v_mfma_f32_16x16x4_f32: one n-tile of 16 channels x 11 k-tiles of 16
-// taps) over the tile's 32 m in steps of 4.  A lane's window offset per k-tile
-// is precomputed (tap -> R * 38 + kz), so every operand read is a ds_read_b32
-// with an immediate offset.  Taps 343..351 read the zero row.  The partial dW
-// leaves through wg_put (fp32 atomics, or the deterministic-mode partials).
-constexpr int SWG_STR = 80;                                      // dz staging row stride (floats)
-__global__ __launch_bounds__(512) void stem_wgrad_kernel(ConvP p, const float* __restrict__ dz,
-                                                         float* __restrict__ dw, WgOut wo, int tz_n,
-                                                         int64_t ntiles, int64_t per_block) {
-    __shared__ float win[2][STEM_WIN];            // 49 rows x 38 z + the zero row
-    __shared__ float dzs[2][STEM_TZ * SWG_STR];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t t_begin = (int64_t)blockIdx.x * per_block;
-    const int64_t t_end = t_begin + per_block < ntiles ? t_begin + per_block : ntiles;
-    if (t_begin >= t_end) return;
-    float* const wp = wo.part ? wo.part + (int64_t)blockIdx.x * wo.pstride : nullptr;
-    if (tid < STEM_WZ) { win[0][49 * STEM_WZ + tid] = 0.0f; win[1][49 * STEM_WZ + tid] = 0.0f; }
-    const size_t plane = (size_t)(p.halo ? p.hdl : p.D), row = (size_t)p.W * plane, img = (size_t)p.H * row;
-    // per tile: window values i = tid + 512 q (q < 4), dz float4 tid
-    float wv[4];
-    float4 dv;
-    auto fetch = [&](int64_t tile) {
-        int64_t t = tile;
-        const int tz = (int)(t % tz_n); t /= tz_n;
-        const int ox = (int)(t % p.OW); t /= p.OW;
-        const int oy = (int)(t % p.OH);
-        const int b = (int)(t / p.OH);
-        const int gy0 = 2 * oy - p.py, gx0 = 2 * ox - p.px, gz0 = tz * STEM_TZ - p.pz;
-        const float* xb = p.a + b * img;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int i = tid + 512 * q;
-            float val = 0.0f;
-            if (i < 49 * STEM_WZ) {
-                const int R = i / STEM_WZ, iz = i - R * STEM_WZ;
-                const int gy = gy0 + R / 7, gx = gx0 + R % 7, gz = gz0 + iz;
-                if (gy >= 0 && gy < p.H && gx >= 0 && gx < p.W && gz >= 0 && gz < p.D) {
-                    if (p.halo) {
-                        const int zl = gz - p.hnlo;
-                        if ((unsigned)zl < (unsigned)p.hdl)
-                            val = xb[gy * row + gx * plane + zl];
-                        else
-                            val = p.halo[(((size_t)b * p.H + gy) * p.W + gx) * (2 * p.hr) +
-                                         (zl < 0 ? zl + p.hr : p.hr + zl - p.hdl)];
-                    } else {
-                        val = xb[gy * row + gx * plane + gz];
-                    }
-                }
-            }
-            wv[q] = val;
-        }
-        const int zi = tid >> 4, c4 = tid & 15;          // 32 rows x 16 float4
-        const int oz = tz * STEM_TZ + zi;
-        dv = oz < p.OD ? *reinterpret_cast<const float4*>(
-                             dz + ((((int64_t)b * p.OH + oy) * p.OW + ox) * p.OD + oz) * 64 + c4 * 4)
-                       : make_float4(0.f, 0.f, 0.f, 0.f);
-    };
-    auto stage = [&](int buf) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (tid + 512 * q < 49 * STEM_WZ) win[buf][tid + 512 * q] = wv[q];
-        *reinterpret_cast<float4*>(&dzs[buf][(tid >> 4) * SWG_STR + (tid & 15) * 4]) = dv;
-    };
-    // this wave: n-tile nt (16 channels), k-tiles kt = kg + 2 j (j < 11) of 16 taps
-    const int nt = wave & 3, kg = wave >> 2;
-    const int l16 = lane & 15, lq = lane >> 4;
-    int abase[11];
-#pragma unroll
-    for (int j = 0; j < 11; ++j) {
-        const int tap = 16 * (kg + 2 * j) + l16;
-        const int R = tap < 343 ? tap / 7 : 49, kz = tap < 343 ? tap % 7 : 0;
-        abase[j] = R * STEM_WZ + kz + lq;
-    }
-    const int bbase = lq * SWG_STR + nt * 16 + l16;
-    floatx4 acc[11];
-#pragma unroll
-    for (int j = 0; j < 11; ++j) acc[j] = floatx4{0.f, 0.f, 0.f, 0.f};
-    fetch(t_begin);
-    stage(0);
-    __syncthreads();
-    int buf = 0;
-    for (int64_t t = t_begin; t < t_end; ++t) {
-        if (t + 1 < t_end) fetch(t + 1);
-        const float* W = win[buf];
-        const float* Z = dzs[buf];
-#pragma unroll
-        for (int s = 0; s < STEM_TZ / 4; ++s) {
-            const float bv = Z[bbase + 4 * s * SWG_STR];
-#pragma unroll
-            for (int j = 0; j < 11; ++j)
-                acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(W[abase[j] + 4 * s], bv, acc[j], 0, 0, 0);
-        }
-        if (t + 1 < t_end) stage(buf ^ 1);
-        __syncthreads();
-        buf ^= 1;
-    }
-#pragma unroll
-    for (int j = 0; j < 11; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int tap = 16 * (kg + 2 * j) + 4 * lq + r;
-            if (tap < 343) wg_put(wo, dw, wp, (int64_t)tap * 64 + nt * 16 + l16, acc[j][r]);
-        }
-}
-
-
-static int launch_stem_wgrad(const ConvP& p, const float* dz, float* dw, hipStream_t s) {
-    const int ncu = num_cus();
-    const int tz_n = (p.OD + STEM_TZ - 1) / STEM_TZ;
-    const int64_t ntiles = (int64_t)p.B * p.OH * p.OW * tz_n;
-    // two workgroups per CU (LDS 2 x 23.4 KB each, 8 waves), >= 8 m-tiles each
-    int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(2 * (int64_t)ncu, (ntiles + 7) / 8));
-    const WgOut wo = wg_out(blocks, 1, 343, 64);
-    const int64_t per = (ntiles + blocks - 1) / blocks;
-    blocks = (ntiles + per - 1) / per;
-    hipLaunchKernelGGL(stem_wgrad_kernel, dim3((unsigned)blocks), dim3(512), 0, s, p, dz, dw, wo, tz_n, ntiles, per);
-    wg_finish(wo, blocks, 1, 343, 64, 343 * 64, dw, s);
-    return check_launch("stem_wgrad_kernel");
-}
-
-static int launch_stem(const ConvP& p, const Epi& e, hipStream_t s) {
-    const int ncu = num_cus();
-    const int tz_n = (p.OD + STEM_TZ - 1) / STEM_TZ;
-    const int64_t ntiles = (int64_t)p.B * p.OH * p.OW * tz_n;
-    // about four workgroups per CU, not one persistent workgroup per CU: the
-    // stem opens the step while the previous step's side-stream work (the
-    // one-CU NMS reduce) may still hold a CU, and a persistent block waiting
-    // for that CU would stall the whole launch (measured 1.5 ms in the step
-    // vs 0.28 ms alone at 128^3); with 4 per CU the others absorb its share
-    // M3D_STEM_X3=1 / 2: the bf16-split forms (measured slower than the f32 kernel: 2.65 / 2.24-2.5 vs
-    // 2.2 ms at 256^3, DESIGN.md round-3 list); default the f32 MFMA kernel
-    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((ntiles + 7) / 8, 4 * (int64_t)ncu));
-    hipLaunchKernelGGL(stem_fwd_kernel, dim3(grid), dim3(512), 0, s, p, e, tz_n, ntiles);
-    return check_launch("stem_fwd_kernel");
 }
 
 extern "C" int m3d_conv3d_fwd_dil(const float* x, int64_t B, int64_t H, int64_t W, int64_t D,

@@ -1,9 +1,10 @@
 // Internal header of the conv sources (gfx950 only).  conv3d.hip holds the
-// convolution kernels and their entry points; two families that reach it only
+// convolution kernels and their entry points; three families that touch it only
 // through host launchers have files of their own:
+//   conv_stem.hip       the one-channel 7^3 stem and its weight gradient (stem_*)
 //   conv_rowsparse.hip  the row-sparse scan and data-gradient scatter (rs_*)
 //   rpn_head_bwd.hip    the RPN head's compact backward (hc_*)
-// A __global__ kernel is defined and launched in one file only (the build has
+// A kernel is defined and launched in one file only (the build has
 // no relocatable device code): a file that needs another's kernel calls the
 // launcher declared here.  Beside those declarations the header holds only
 // what both sides compile: kernel-argument structs, constants and
@@ -12,6 +13,113 @@
 #include "common.h"
 
 namespace m3d {
+
+typedef float floatx16 __attribute__((ext_vector_type(16)));
+
+struct ConvP {
+    const float* a;   // A source (x or dz), channels-last [B,H,W,D,C]
+    int B, H, W, D, C;
+    int OH, OW, OD;   // M grid
+    int kh, kw, kd;
+    int sy, sx, sz;
+    int py, px, pz;
+    int64_t M;
+    int K;            // taps * C
+    const float* w;
+    int N;
+    int flip;         // bwd-data: use tap (taps-1-t)
+    // batched GEMMs (Winograd points): blockIdx.z selects the batch; A, W and Y
+    // advance by these element strides (0 for ordinary convs)
+    int64_t bsa, bsw, bsy;
+    int dly = 1, dlx = 1, dlz = 1;   // dilation (mrcnn_mask_conv3b: fwd, bwd-data on the flipped taps, bwd-weight)
+    int nbatch = 1;                  // batches (PERSIST: looped inside the grid)
+    // depth-slab halo planes beside the slab (the stem and the direct weight
+    // gradient, m3d_conv3d_*_halo): the conv runs on the virtual z grid
+    // [lower halo (hnlo planes) | slab (hdl) | upper halo], D = its depth; x (a)
+    // holds the slab [B,H,W,hdl,C], halo [B,H,W,2*hr,C] the neighbours' planes
+    // ([0,hr) from below, [hr,2hr) from above)
+    const float* halo = nullptr;
+    int hnlo = 0, hdl = 0, hr = 0;
+};
+
+struct Epi {
+    const float* bias;
+    const float* scale;
+    const float* shift;
+    const float* res;
+    int res_mode;
+    int relu;
+    float* z;
+    float* y;
+    int64_t ldy;
+    float* y2;
+    int64_t ldy2;
+    int split;
+    int YH, YW, YD;
+    int ysy, ysx, ysz;
+    int accumulate;
+    int simple;       // y row == m (same grid, unit store stride)
+    // depth-slab halo (wino_output_kernel<.., HALO>): output z over the
+    // halo-extended grid; planes [hlo, hlo + dl) go to y (depth dl), the halo
+    // planes to yh [B][H][W][2][N] (plane 0 below, 1 above)
+    float* yh;
+    int hlo, dl;
+    int deconv = 0;   // > 0: 2x2x2 stride-2 transposed conv, n = tap * deconv + o
+    // fused BN-ReLU backward of the unit that produced this data gradient's
+    // input (m3d_conv3d_bwd_data_bn): the stored value t (after accumulate) is
+    // the unit's output gradient; written instead are dz = act'(t) * scale
+    // (into y), dpre = act'(t) (into fdres, if set), and per-tile channel sums
+    // of dpre, dpre * xhat, dz (rows of fpart, [3][rows][N]) -- the maths of
+    // bn_act_bwd_kernel
+    int fbn = 0, frelu = 0;
+    const float* fy = nullptr;
+    const float* fz = nullptr;
+    const float* fscale = nullptr;
+    const float* fmean = nullptr;
+    const float* frstd = nullptr;
+    float* fdres = nullptr;
+    float* fpart = nullptr;
+    int64_t fprows = 0;           // partial rows (stride of the three sum planes)
+};
+
+// activation codes (Epi::relu): 0 none, 1 ReLU, 2 sigmoid (mrcnn_mask)
+__device__ __forceinline__ float act(int code, float v) {
+    if (code == 1) return v > 0.0f ? v : 0.0f;
+    if (code == 2) return 1.0f / (1.0f + expf(-v));
+    return v;
+}
+
+// 16-byte loads / stores of four consecutive floats
+__device__ __forceinline__ float4 ld4(const float* q) { return *reinterpret_cast<const float4*>(q); }
+__device__ __forceinline__ void st4(float* q, const float4& v) { *reinterpret_cast<float4*>(q) = v; }
+
+// -------------------------------------------------------------------------
+// Weight-gradient epilogue target.  Default: fp32 atomics into C (the m-splits
+// of a tile arrive in any order, so the last bits vary run to run).
+// Deterministic mode (m3d_set_deterministic): each split stores its tile into
+// part[split][batch][K][N] of the registered scratch and wg_reduce_kernel adds
+// the splits to C in split order; with a single split (the scratch too small
+// for two), the one writer of each element adds to C without an atomic.
+// Store (either mode): the caller declared C uninitialised scratch (`fresh`,
+// the Winograd-domain dW_hat) and the launcher settled on one split of a
+// non-stream-K grid, so each (batch, k, n) has exactly one writer, which
+// stores its sum: no zero-fill before the launch and no read of C
+// (wg_settle).  Every other fresh launch is preceded by the fill.
+// -------------------------------------------------------------------------
+struct WgOut {
+    float* part;
+    int64_t pstride;      // floats per split (nbatch * K * N)
+    int plain;
+    int store;
+    const int* gate;      // row-sparse gate (bwd_weight_wino): the workgroup returns when *gate != 0; NULL: ungated
+};
+
+__device__ __forceinline__ void wg_put(const WgOut& o, float* C, float* P, int64_t idx, float v) {
+    if (P) P[idx] = v;
+    else if (o.store) C[idx] = v;
+    else if (o.plain) C[idx] += v;
+    else unsafeAtomicAdd(C + idx, v);
+}
 
 // the exact 3-way bf16 split of an fp32 value (conv3d.hip, "exact 3-way bf16 split", says why it is exact)
 __device__ __forceinline__ uint32_t bf16_bits(float x) {
@@ -71,6 +179,17 @@ __device__ __forceinline__ void rs_copy_row(const float* __restrict__ s, float* 
 }
 
 // ---- host functions called across files (defined in the file named) ----------
+// conv3d.hip: the chip's CU count, and the weight-gradient target of a launch (WgOut above; wg_finish
+// runs wg_reduce_kernel)
+int num_cus();
+WgOut wg_out(int64_t& splits, int64_t nbatch, int64_t K, int64_t N);
+void wg_finish(const WgOut& o, int64_t splits, int64_t nbatch, int64_t K, int64_t N, int64_t bsc, float* C,
+               hipStream_t s);
+// conv_stem.hip: stem_ok: the conv is the one-channel 7^3 stem with an epilogue the stem kernels cover
+bool stem_ok(int64_t Cin, int kh, int kw, int kd, int64_t Cout, int sy, int sx, int sz, int dly, int dlx, int dlz,
+             int res_mode, int64_t split_n, int64_t ldy);
+int launch_stem(const ConvP& p, const Epi& e, hipStream_t s);
+int launch_stem_wgrad(const ConvP& p, const float* dz, float* dw, hipStream_t s);
 // conv3d.hip: the point GEMMs M[xi] = U[xi] V[xi] on split planes (x3_gemm*_kernel), the bf16-split
 // weight-gradient GEMM C[b] += A[b]^T B[b] (x3_wgrad*_kernel), split3_kernel
 void launch_gemm_x3(const float* U, const float* V, float* Mo, int64_t T, int K, int N, int P, hipStream_t s,
